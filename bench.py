@@ -13,10 +13,15 @@ Weak scaling: every rank processes --batch crops per step.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (schema in the task contract) with `roofline` (dominant kernel
-class = the 3x3 implicit-GEMM convolutions, fp32 MFMA, timed with HIP events on the launch
-stream inside the timed region) and `cpu_baseline` (the torch-fp32 oracle port of the same
-step, on the host cores, bounded sample).
+Rank 0 prints ONE JSON line (schema in the task contract).  A plain run sets up, warms up, times
+--steps steps and prints the line; it measures nothing else.  --full adds what the headline does
+not need: `roofline` (dominant kernel class = the 3x3 implicit-GEMM convolutions, timed with HIP
+events on the launch stream inside the timed region), the per-class kernel table of a few
+un-timed steps after it, and `cpu_baseline` (the torch-fp32 oracle port of the same step, on the
+host cores, bounded sample).
+
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
+Inputs and weights come from fixed seeds: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -76,12 +81,25 @@ def physical_cores():
     return os.cpu_count() or 1
 
 
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, bounded by a cgroup v2 CPU quota (a container sees the host's cores in
+    /proc/cpuinfo; threads beyond its share only slow the baseline down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    try:
+        quota, period = open('/sys/fs/cgroup/cpu.max').read().split()
+        if quota != 'max':
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n
+
+
 def cpu_baseline(H, W, budget_s=240.0):
     """The reference's train step restated on torch-CPU fp32 (oracle/net_torch.py + oracle/noise_np.py), timed on this
     box's host cores by the protocol of BASELINE.md section 3: per crop `sample_params_max('SonyA7S2')` ->
     `generate_noisy_torch('pr', clip=2)` -> clamp -> UNetSeeInDark nf=32 forward -> L1(clamp) -> backward -> Adam(lr 1e-4),
     `np.random.seed(1997 + step)`, `torch.manual_seed(1997)`, 2 warm-up + 5 timed steps per leg:
-      * all PHYSICAL cores (torch.set_num_threads(physical_cores())) on B = 16 crops of 4 x H x W   -> `value`
+      * all PHYSICAL cores this process may use (min(physical_cores(), usable_cpus()) threads) on B = 16 crops of 4 x H x W -> `value`
       * one thread (the reference exports OMP_NUM_THREADS=1, utils/utils.py:2) on B = 1 crop        -> `one_thread`
     with the four buckets the reference's tqdm line shows (trainer_SID.py:81-123): dataloader (here: synthetic clean crops),
     preprocess (parameters + sampler + clamp), net (forward), bp (loss + backward + Adam).
@@ -96,7 +114,7 @@ def cpu_baseline(H, W, budget_s=240.0):
     from oracle import net_torch as O, noise_np as N
     from pnnp_amd import process as P                      # host-side parameter tables / draws (no device code)
     ncpu = os.cpu_count() or 1
-    all_cores = physical_cores()
+    all_cores = min(physical_cores(), usable_cpus())
 
     def leg(threads, batch, warm, timed, budget):
         torch.set_num_threads(threads)
@@ -221,6 +239,30 @@ def csrc_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 63_000_000       # --dump-outputs writes less than 64 MB in all
+
+
+def dump_outputs(d, loss, net):
+    """What the caller of the timed step holds after its last call, as float32 DIR/<name>.npy:
+      loss    [1 + B]  HipTrainStep.step's return value: the mean L1 loss, then the SSE of each crop
+      params  the network's weights after that step's Adam update, flattened in named_parameters() order
+      grad    the gradient that update used (net.engine.params.grad), in the same order
+    When params + grad exceed the limit, both keep the same fixed, seeded sample of positions."""
+    import numpy as np
+    named = list(net.named_parameters())
+    params = np.concatenate([p.detach().reshape(-1).cpu().numpy() for _, p in named])
+    grad = np.concatenate([net.engine.params.grad_view(n, (p.numel(),)).cpu().numpy() for n, p in named])
+    out = {'loss': loss.detach().cpu().numpy()}
+    keep = (DUMP_LIMIT_BYTES - out['loss'].nbytes) // 8
+    if params.size > keep:
+        idx = np.sort(np.random.default_rng(0).choice(params.size, keep, replace=False))
+        params, grad = params[idx], grad[idx]
+    out['params'], out['grad'] = params, grad
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + '.npy'), v.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -244,8 +286,15 @@ def main():
     ap.add_argument('--overlap-allreduce', action='store_true',
                     help='N > 1: launch the gradient all-reduce in buckets from inside the backward pass (default: one collective after it; '
                          'the persistent convolution kernels need every CU, see pnnp_amd.trainer.BucketedAllReduce)')
-    ap.add_argument('--no-kernel-events', action='store_true', help='skip per-launch HIP events (roofline becomes whole-step)')
+    ap.add_argument('--no-kernel-events', action='store_true', help='with --full: skip per-launch HIP events (roofline becomes whole-step)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline number does not need: the dominant kernel\'s roofline (HIP events in the timed region), '
+                         'the per-class kernel table of a few un-timed steps, and the CPU baseline (N=1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    kernel_events = args.full and not args.no_kernel_events
 
     import numpy as np
     import torch
@@ -333,7 +382,7 @@ def main():
     pol = net.engine.policy
     fam0 = ('h2' if getattr(pol, 'h2', False) else 'x3') if pol.x3 else ('wino' if pol.wino else 'direct')
     dom_kinds = set(FAMILY[fam0][2])
-    if not args.no_kernel_events:
+    if kernel_events:
         ops.PROFILE, ops.PROFILE_KINDS = [], dom_kinds
     if ts.reducer is not None:
         ts.reducer.time_waits = True            # one event pair per step around reducer.finish(): is the all-reduce hidden?
@@ -348,8 +397,11 @@ def main():
     if ts.reducer is not None:
         ts.reducer.time_waits = False
     prof, ops.PROFILE, ops.PROFILE_KINDS = ops.PROFILE, None, None
+    loss_val = float(loss[0])                   # (the loss buffer is reused: read it before the un-timed steps below)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, net)
     prof_all, extra_steps = None, 3
-    if not args.no_kernel_events:
+    if kernel_events:
         ops.PROFILE = []
         for i in range(extra_steps):
             one_step(args.warmup + args.steps + i)
@@ -368,7 +420,6 @@ def main():
     elif waits:
         per_rank = torch.tensor([[1e3 * dt_own / args.steps, sum(waits) / len(waits), max(waits)]], dtype=torch.float64)
     dt = float(tmax.item())
-    loss_val = float(loss[0])
     if not np.isfinite(loss_val):
         # a number measured on a diverged network is not a measurement (NaN / inf operands even run FASTER on this power-limited chip)
         raise SystemExit(f'bench: the training loss is {loss_val} after {args.warmup + args.steps} steps: the step is broken, no throughput is reported')
@@ -479,9 +530,10 @@ def main():
                 out["mfma_time_frac_of_step"] = sum(v[3] for v in call.values()) / extra_steps / (dt / args.steps)
         else:
             out["roofline"] = {"bound": "mfma", "achieved": None, "peak": FAMILY[fam0][1], "unit": "TFLOP/s", "frac": None, "traffic": None,
-                               "kernel": "not measured (--no-kernel-events)", "step_algorithmic_tflops": step_tflops}
+                               "kernel": "not measured (--no-kernel-events)" if args.full else "not measured (plain run; --full measures it)",
+                               "step_algorithmic_tflops": step_tflops}
         out["step_tflops_per_gpu"] = step_tflops
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, S, args.cpu_baseline_seconds)
         # RCCL prints its version banner through C stdio (block-buffered when piped): push that out first so that the JSON line is the
         # last line on stdout, then keep the communicator alive until after the print (its teardown prints nothing)

@@ -16,16 +16,16 @@ timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -25 > $OUT/pytest.log
 timeout 300 python -m pytest tests/test_gpu_x3.py tests/test_gpu_fullsize.py -q -m gpu -s -k "accurate or golden or cancellation or dynamic_range or below or signed" 2>&1 | grep -i "relative L2\|worst HIP\|vs float64\|cancellation\|scale x\|below the\|signed mean\|convT wgrad" > $OUT/accuracy.log
 fi
 # 3. the bench line (default flags: complete CPU-baseline protocol) and the rocprofv3 kernel statistics of the same command
-timeout 1200 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 export TMPDIR=/tmp; cd /tmp; rm -rf /tmp/rp_*
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/rp_b -o b --output-format csv -- python3 /root/repo/bench.py --steps 6 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof_bench.err
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/rp_b -o b --output-format csv -- python3 "$OLDPWD/bench.py" --full --steps 6 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof_bench.err
 cp $(find /tmp/rp_b -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 cd /root/repo
-timeout 600 python bench.py --steps 20 --warmup 5 --family wino --no-cpu-baseline > $OUT/bench_family_wino.json 2> /dev/null
+timeout 600 python bench.py --full --steps 20 --warmup 5 --family wino --no-cpu-baseline > $OUT/bench_family_wino.json 2> /dev/null
 # 4. config 5 (ResUnet + NoiseFlow proxy, B=12)
-timeout 600 python bench.py --arch resunet --noise noiseflow --batch 12 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config5.json 2> $OUT/bench_config5.err
+timeout 600 python bench.py --full --arch resunet --noise noiseflow --batch 12 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_config5.json 2> $OUT/bench_config5.err
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/rp_c5 -o c --output-format csv -- python3 /root/repo/bench.py --arch resunet --noise noiseflow --batch 12 --steps 4 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_under_rocprof.json 2> /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/rp_c5 -o c --output-format csv -- python3 "$OLDPWD/bench.py" --full --arch resunet --noise noiseflow --batch 12 --steps 4 --warmup 2 --no-cpu-baseline > $OUT/bench_config5_under_rocprof.json 2> /dev/null
 cp $(find /tmp/rp_c5 -name "*kernel_stats.csv" | head -1) $OUT/bench_config5_kernel_stats.csv
 cd /root/repo
 # 5. matrix-pipe utilisation per layer (PMC), with the co-execution and wait counters
