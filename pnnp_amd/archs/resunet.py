@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import PnnpError
-from .unet import FlatParams, _Bufs, _EngineBase, RELU
+from .plan import resolve_resunet
+from .unet import FlatParams, _Bufs, _EngineBase, _Slots, RELU
 
 
 class _ConvHolder(nn.Module):      # modules.py:140-153 convWithBN(is_bn=False): .conv = Sequential(conv=Conv2d(bias=False))
@@ -55,6 +56,19 @@ class ResUnetEngine(_EngineBase):
         self.cout = module.out_nc
         self.cout_pad = (self.cout + 7) // 8 * 8
 
+    def _resolve(self, pol, train, B, H, W):
+        return resolve_resunet(self.ch, self.cin, self.cout, pol, train, B, H, W)
+
+    @staticmethod
+    def _pname(name):
+        """the parameter names (weight, bias or None) of a layer of the plan"""
+        if name[0] == 'b':
+            return f'conv{name[1]}.block.{name[3]}.conv.conv.weight', None
+        if name.startswith('sc'):
+            return f'conv{name[2]}.short_cut.0.conv.conv.weight', None
+        stem = name + '.conv' if name.startswith('pool') else name
+        return stem + '.weight', stem + '.bias'
+
     # ---------------------------------------------------------------- weights
     def _buf(self, key, n, dev, dtype=torch.float32):
         k = (key, dev)
@@ -66,143 +80,51 @@ class ResUnetEngine(_EngineBase):
         """channels of the NHWC loss gradient backward() wants (UNetEngine.grad_out_channels)"""
         return 4 if (self.cout == 4 and self._pol.use_thin_head(self.ch[0], self.cout, B * H * W)) else self.cout_pad
 
-    def pack_weights(self, train):
-        """Re-pack every layer's weights for the kernels; the job table is built once per device / mode / parameter storage
-        and runs in a few launches per step (ops.PackJobs)."""
-        dev = self.params.flat.device
-        P = dict(self.m.named_parameters())
-        key = (dev, train, self._pol.key(), tuple(p.data_ptr() for p in P.values()))
-        if self._jobs_key != key:
-            self._jobs, self._jobs_key = self._build_pack_jobs(train, dev, P), key
-        self._jobs.run()
-
-    def _build_pack_jobs(self, train, dev, P):
+    def _build_pack_jobs(self, train, dev, P, plan):
+        """One record per layer, in the plan's families: self._wp[name] = (forward pack, backward-data pack, the weight's amax slot)."""
         jobs = ops.PackJobs(cap=512)
-        W = {}
-        self.WU, self.WX = {}, {}
-        self.WH, self.WS = {}, {}              # fp16x2 packs (forward, backward-data) per layer; the weight tensor's amax slot (csrc/h2.h)
-        self.WM = {}                           # pointwise / stride-2 / ConvTranspose2d layers on the fp16x2 GEMM kernel (csrc/gemm_h2s.hip): kind-6 packs
-        h2pw = self._pol.h2 and self._pol.h2_pointwise
-        def conv(name, pname, cin_pad=None, cout_pad=None, dgrad=True, c1=None):
-            w = P[pname]
-            co, ci, kh, kw = w.shape
-            t = kh * kw
-            cip = cin_pad or ci
-            bwd = train and dgrad
-            xf, xd = self._pol.use_x3(co, cip, t, c1)
-            xd = xd and bwd
-            hf, hd = self._pol.use_h2(co, cip, t, c1)
-            hf, hd = hf and xf, hd and xd
-            if hf or hd:                                               # the fp16x2 kernel takes what bf16x3 would have taken
-                self.WH[name] = (self._buf(name + ':h2f', ops.h2_weight_bytes(cip, co), dev, torch.uint8) if hf else None,
-                                 self._buf(name + ':h2d', ops.h2_weight_bytes(co, ci), dev, torch.uint8) if hd else None)
-                self.WS[name] = jobs.add_h2(w, self.WH[name][0], self.WH[name][1], cin_pad=(cip + 15) // 16 * 16)
-                xf, xd = xf and not hf, xd and not hd
-            p1 = t == 1 and self._pol.use_x3_pointwise(ci, co) and self._pol.use_x3_pointwise(co, ci) and (c1 is None or c1 % 32 == 0)
-            if p1 and h2pw and ops.gemm_h2_supported(c1 if c1 else ci, co) and ops.gemm_h2_supported(co, ci):
-                mf = self._buf(name + ':h2mf', ops.h2mat_bytes(ci, co), dev, torch.uint8)
-                md = self._buf(name + ':h2md', ops.h2mat_bytes(co, ci), dev, torch.uint8) if bwd else None
-                self.WS[name] = jobs.add_h2_1x1(w, mf, md)
-                W[name] = (None, None); self.WU[name] = (None, None); self.WM[name] = (mf, md if bwd else mf)
-                return
-            if p1:                                                     # 1x1 (ResidualBlock shortcut) on the pointwise bf16x3 kernel
-                x3f = self._buf(name + ':x3f', ops.x3mat_bytes(ci, co), dev, torch.uint8)
-                x3d = self._buf(name + ':x3d', ops.x3mat_bytes(co, ci), dev, torch.uint8) if bwd else None
-                jobs.add_x3_1x1(w, x3f, x3d)
-                W[name] = (None, None); self.WU[name] = (None, None); self.WX[name] = (x3f, x3d if bwd else x3f)
-                return
-            wf, wd = self._wino(co, ci, t)
-            wf, wd = wf and not (xf or hf), wd and bwd and not (xd or hd)
-            df, dd = not (xf or wf or hf), bwd and not (xd or wd or hd)        # what is left for the direct fp32 kernels
-            f = self._buf(name + ':f', t * cip * co, dev) if df else None
-            d = self._buf(name + ':d', t * (cout_pad or co) * ci, dev) if dd else None
-            if df or dd:
-                jobs.add_conv(w, f, d, cin_pad=cin_pad, cout_pad=cout_pad)
-            uf = self._buf(name + ':uf', 16 * co * ci, dev) if wf else None
-            ud = self._buf(name + ':ud', 16 * co * ci, dev) if wd else None
-            if wf or wd:
-                jobs.add_wino(w, uf, ud)
-            x3f = self._buf(name + ':x3f', ops.x3_weight_bytes(cip, co), dev, torch.uint8) if xf else None
-            x3d = self._buf(name + ':x3d', ops.x3_weight_bytes(co, ci), dev, torch.uint8) if xd else None
-            if xf or xd:
-                jobs.add_x3(w, x3f, x3d, cin_pad=(cip + 15) // 16 * 16)
-            W[name] = (f, d)
-            self.WU[name] = (uf, ud)
-            self.WX[name] = (x3f, x3d)
-        conv('conv_in', 'conv_in.weight', cin_pad=self.cin_pad, dgrad=False)
-        for i in range(1, 10):
-            conv(f'b{i}_0', f'conv{i}.block.0.conv.conv.weight', c1=self.ch[9 - i] if i >= 6 else None)     # decoder: cat([up, skip])
-            conv(f'b{i}_1', f'conv{i}.block.1.conv.conv.weight')
-            if i >= 6:
-                conv(f'sc{i}', f'conv{i}.short_cut.0.conv.conv.weight', c1=self.ch[9 - i])
-        for l in range(1, 5):
-            w = P[f'pool{l}.conv.weight']
-            co, ci = w.shape[0], w.shape[1]
-            if h2pw and self._pol.use_x3_pointwise(ci, co) and ops.gemm_h2_supported(ci, co) and ops.gemm_h2_supported(co, ci):
-                f = self._buf(f'pool{l}:h2mf', ops.h2mat_bytes(9 * ci, co), dev, torch.uint8)
-                d = self._buf(f'pool{l}:h2md', 9 * ops.h2mat_bytes(co, ci), dev, torch.uint8) if train else None
-                self.WS[f'pool{l}'] = jobs.add_h2_s2(w, f, d)
-                self.WM[f'pool{l}'] = (f, d if train else f)
+        self._wp = {}
+        u8 = torch.uint8
+        for name, s in plan.steps.items():
+            w = P[self._pname(name)[0]]
+            pf, pd = s.pack
+            b = lambda kind, n, dt=u8: self._buf(name + kind, n, dev, dt)
+            kind = 's2' if name.startswith('pool') else 'convt' if name.startswith('upv') else '1x1' if w.shape[-1] == 1 else None
+            co, ci = (w.shape[1], w.shape[0]) if kind == 'convt' else (w.shape[0], w.shape[1])
+            if kind and pf in ('h2', 'x3'):    # 3x3 stride 2, ConvTranspose2d 2x2 stride 2, 1x1: the pointwise fp16x2 / bf16x3 GEMM kernels
+                mat = ops.h2mat_bytes if pf == 'h2' else ops.x3mat_bytes
+                fn, dn = dict(s2=(mat(9 * ci, co), 9 * mat(co, ci)), convt=(mat(ci, 4 * co), mat(4 * co, ci)), **{'1x1': (mat(ci, co), mat(co, ci))})[kind]
+                f, d = b(':h2mf' if pf == 'h2' else ':x3f', fn), b(':h2md' if pf == 'h2' else ':x3d', dn) if pd else None
+                self._wp[name] = (f, d, getattr(jobs, f'add_{pf}_{kind}')(w, f, d))
                 continue
-            if self._pol.use_x3_pointwise(ci, co) and self._pol.use_x3_pointwise(co, ci):      # stride-2 conv on the pointwise bf16x3 kernel
-                f = self._buf(f'pool{l}:x3f', ops.x3mat_bytes(9 * ci, co), dev, torch.uint8)
-                d = self._buf(f'pool{l}:x3d', 9 * ops.x3mat_bytes(co, ci), dev, torch.uint8) if train else None
-                jobs.add_x3_s2(w, f, d)
-                self.WX[f'pool{l}'] = (f, d if train else f)
+            if kind in ('s2', 'convt'):        # the direct kernels (their own weight layouts)
+                f, d = b(':f', w.numel(), torch.float32), b(':d', w.numel(), torch.float32) if pd else None
+                if kind == 'convt':
+                    jobs.add_convt(w, f, d)
+                else:
+                    jobs.add_conv(w, f, None)
+                    if pd:
+                        jobs.add_s2_dgrad(w, d)
+                self._wp[name] = (f, d, None)
                 continue
-            f = self._buf(f'pool{l}:f', w.numel(), dev)
-            jobs.add_conv(w, f, None)
-            d = None
-            if train:
-                d = self._buf(f'pool{l}:d', w.numel(), dev)
-                jobs.add_s2_dgrad(w, d)
-            W[f'pool{l}'] = (f, d)
-        for i in range(6, 10):
-            w = P[f'upv{i}.weight']
-            ci, co = w.shape[0], w.shape[1]
-            # (only beside an fp16x2 shortcut: its backward-data leaves the amax slot of the summed gradient this layer's backward splits)
-            if h2pw and f'sc{i}' in self.WM and self._pol.use_x3_pointwise(ci, 4 * co) and ops.gemm_h2_supported(ci, 4 * co) and ops.gemm_h2_supported(co, ci):
-                f = self._buf(f'upv{i}:h2mf', ops.h2mat_bytes(ci, 4 * co), dev, torch.uint8)
-                d = self._buf(f'upv{i}:h2md', ops.h2mat_bytes(4 * co, ci), dev, torch.uint8) if train else None
-                self.WS[f'upv{i}'] = jobs.add_h2_convt(w, f, d)
-                self.WM[f'upv{i}'] = (f, d if train else f)
-                continue
-            if self._pol.use_x3_pointwise(ci, 4 * co) and self._pol.use_x3_pointwise(co, ci):
-                f = self._buf(f'upv{i}:x3f', ops.x3mat_bytes(ci, 4 * co), dev, torch.uint8)
-                d = self._buf(f'upv{i}:x3d', ops.x3mat_bytes(4 * co, ci), dev, torch.uint8) if train else None
-                jobs.add_x3_convt(w, f, d)
-                self.WX[f'upv{i}'] = (f, d if train else f)
-                continue
-            f = self._buf(f'upv{i}:f', w.numel(), dev)
-            d = self._buf(f'upv{i}:d', w.numel(), dev) if train else None
-            jobs.add_convt(w, f, d)
-            W[f'upv{i}'] = (f, d)
-        conv('conv10', 'conv10.weight', cout_pad=self.cout_pad)
-        self.W = W
+            kh, kw = w.shape[2], w.shape[3]
+            cip = self.cin_pad if name == 'conv_in' else ci
+            got, slot = {}, None
+            if 'h2' in (pf, pd):                               # the fp16x2 kernel takes what bf16x3 would have taken
+                got['h2'] = (b(':h2f', ops.h2_weight_bytes(cip, co)) if pf == 'h2' else None, b(':h2d', ops.h2_weight_bytes(co, ci)) if pd == 'h2' else None)
+                slot = jobs.add_h2(w, *got['h2'], cin_pad=(cip + 15) // 16 * 16)
+            if 'direct' in (pf, pd):
+                got['direct'] = (b(':f', kh * kw * cip * co, torch.float32) if pf == 'direct' else None,
+                                 b(':d', kh * kw * (self.cout_pad if name == 'conv10' else co) * ci, torch.float32) if pd == 'direct' else None)
+                jobs.add_conv(w, *got['direct'], cin_pad=cip, cout_pad=self.cout_pad if name == 'conv10' else co)
+            if 'wino' in (pf, pd):
+                got['wino'] = (b(':uf', 16 * co * ci, torch.float32) if pf == 'wino' else None, b(':ud', 16 * co * ci, torch.float32) if pd == 'wino' else None)
+                jobs.add_wino(w, *got['wino'])
+            if 'x3' in (pf, pd):
+                got['x3'] = (b(':x3f', ops.x3_weight_bytes(cip, co)) if pf == 'x3' else None, b(':x3d', ops.x3_weight_bytes(co, ci)) if pd == 'x3' else None)
+                jobs.add_x3(w, *got['x3'], cin_pad=(cip + 15) // 16 * 16)
+            self._wp[name] = (got[pf][0], got[pd][1] if pd else None, slot)
         return jobs
-
-    def _wino(self, co, ci, taps=9):
-        """(forward, backward-data) through the Winograd F(2x2,3x3) kernel?  Same rule as the UNet engine (self.policy)."""
-        return self._pol.use_wino(co, ci, taps)
-
-    def _cf(self, name, src, src2, bias, out, cout, act, residual=None):
-        """3x3 forward: bf16x3 / Winograd kernel where packed for it, else the direct implicit GEMM."""
-        x3 = self.WX.get(name, (None, None))[0]
-        if x3 is not None:
-            return ops.conv_x3_fwd(src, src2, x3, bias, out, cout, act, residual=residual)
-        u = self.WU.get(name, (None, None))[0]
-        if u is not None:
-            return ops.conv_wino_fwd(src, src2, u, bias, out, cout, act, residual=residual)
-        return ops.conv_fwd(src, src2, self.W[name][0], bias, out, cout, 9, act, residual=residual)
-
-    def _dg(self, name, gsrc, dx1, **kw):
-        x3 = self.WX.get(name, (None, None))[1]
-        if x3 is not None:
-            return ops.conv_x3_bwd_data(gsrc, x3, dx1, **kw)
-        u = self.WU.get(name, (None, None))[1]
-        if u is not None:
-            return ops.conv_wino_bwd_data(gsrc, u, dx1, **kw)
-        return ops.conv_bwd_data(gsrc, self.W[name][1], dx1, **kw)
 
     # ---------------------------------------------------------------- forward
     def forward(self, x, train, reflect_pad=0, add_residual=True):
@@ -225,50 +147,33 @@ class ResUnetEngine(_EngineBase):
         # packed weights are re-used while no parameter changed (eval loops); in-place torch updates bump
         # tensor._version, the fused Adam kernel goes through mark_dirty()
         self._pol = self.effective_policy(H, Wd, max(self.ch[0], self.cin_pad, self.cout_pad))
-        self._packs_ready(train, dev)
+        plan = self._plan = self._plan_for(B, H, Wd, train)
+        self._packs_ready(train, dev, plan)
         gen = self._begin_forward((B, H, Wd, dev), train)
         bufs = self.bufs.setdefault((B, H, Wd, dev), _Bufs())
         P = dict(self.m.named_parameters())
-        ch, W = self.ch, self.W
+        ch = self.ch
         g = lambda n, s: bufs.get(n, s, dev)
         hs = [H >> i for i in range(5)]; ws = [Wd >> i for i in range(5)]
         a = {}
         a['x8'] = ops.nchw_to_nhwc(x, g('x8', (B, H, Wd, self.cin_pad)), self.cin_pad, reflect_pad=reflect_pad)
         # fp16x2 family (csrc/h2.h): amax slots of the activations, keyed by the layer that wrote the tensor; sign bits of the ReLU outputs
         # that backward-data will need as masks
-        h2_on = bool(self.WH) or bool(self.WM)       # amax-slot upkeep whenever ANY layer runs on an fp16x2 kernel
-        if h2_on:
-            bufs.slots('f', dev).zero_()
-        sl = lambda n: bufs.slot('f', n, dev)
-        src_name = {}
-
-        def produced(t, name, fused):
-            src_name[id(t)] = name
-            if h2_on and not fused:
-                ops.amax(t, sl(name))
-            return t
-
-        def fslot(t, name):                        # the amax slot of an activation an fp16x2 kernel is about to split (filled here if nobody did)
-            if id(t) not in src_name:
-                produced(t, name, fused=False)
-            return sl(src_name[id(t)])
+        T = _Slots(bufs, 'f', dev, plan.h2)
+        sl = T.slot
 
         def cf(name, src, src2, bias, out, cout, act, residual=None):
-            hp = self.WH.get(name, (None, None))[0]
-            if hp is None:
-                return produced(self._cf(name, src, src2, bias, out, cout, act, residual=residual), name, fused=False)
             bits = None
-            if train and act != 0 and residual is None:
-                bits = a['bits:' + name] = bufs.bits(name, B, out.shape[1], out.shape[2], cout, dev)
-            if id(src) not in src_name:                                # (the zero-padded network input: a kernel of its own fills its slot)
-                produced(src, 'in:' + name, fused=False)
-            ops.conv_h2_fwd(src, src2, hp, self.WS[name], bias, out, cout, act, sl(src_name[id(src)]),
-                            sl(src_name[id(src2)]) if src2 is not None else None, amax_y=sl(name), bits_y=bits, residual=residual)
-            return produced(out, name, fused=True)
+            if plan[name].fwd == 'h2':
+                if train and act != 0 and residual is None:
+                    bits = a['bits:' + name] = bufs.bits(name, B, out.shape[1], out.shape[2], cout, dev)
+                if src is a['x8']:                              # (the zero-padded network input: a kernel of its own fills its slot)
+                    T.put(src, 'in:' + name, fused=False)
+            return self._conv3_fwd(plan, name, T, src, src2, bias, out, cout, act, bits=bits, residual=residual)
 
-        if self._pol.use_thin_first(self.cin, ch[0], H, Wd, a['x8'].shape[3]):
-            a['t0'] = produced(ops.first_fwd(a['x8'], P['conv_in.weight'], P['conv_in.bias'], g('t0', (B, H, Wd, ch[0])), RELU,
-                                             amax_y=sl('conv_in') if h2_on else None), 'conv_in', fused=True)
+        if plan['conv_in'].fwd == 'thin':
+            a['t0'] = T.put(ops.first_fwd(a['x8'], P['conv_in.weight'], P['conv_in.bias'], g('t0', (B, H, Wd, ch[0])), RELU,
+                                          amax_y=sl('conv_in') if plan.h2 else None), 'conv_in', fused=True)
         else:
             a['t0'] = cf('conv_in', a['x8'], None, P['conv_in.bias'], g('t0', (B, H, Wd, ch[0])), ch[0], RELU)
         xin = a['t0']
@@ -278,260 +183,162 @@ class ResUnetEngine(_EngineBase):
             a[f't{l}'] = cf(f'b{l}_0', xin, None, None, g(f't{l}', shp), ch[lv], RELU)
             a[f'c{l}'] = cf(f'b{l}_1', a[f't{l}'], None, None, g(f'c{l}', shp), ch[lv], 0, residual=xin)
             if l < 5:
-                if f'pool{l}' in self.WM:
-                    a[f'd{l}'] = produced(ops.conv_s2_h2_fwd(a[f'c{l}'], fslot(a[f'c{l}'], f'c{l}'), self.WM[f'pool{l}'][0], self.WS[f'pool{l}'], P[f'pool{l}.conv.bias'],
-                                                             g(f'd{l}', (B, hs[l], ws[l], ch[l])), ch[l], 0, amax_y=sl(f'pool{l}')), f'pool{l}', fused=True)
-                elif f'pool{l}' in self.WX:
-                    a[f'd{l}'] = produced(ops.conv_s2_x3_fwd(a[f'c{l}'], self.WX[f'pool{l}'][0], P[f'pool{l}.conv.bias'],
-                                                             g(f'd{l}', (B, hs[l], ws[l], ch[l])), ch[l], amax_y=sl(f'pool{l}') if h2_on else None), f'pool{l}', fused=True)
+                name, c = f'pool{l}', a[f'c{l}']
+                f, _, wslot = self._wp[name]
+                y = g(f'd{l}', (B, hs[l], ws[l], ch[l]))
+                if plan[name].fwd == 'h2':
+                    ops.conv_s2_h2_fwd(c, T.of(c), f, wslot, P[name + '.conv.bias'], y, ch[l], 0, amax_y=sl(name))
+                elif plan[name].fwd == 'x3':
+                    ops.conv_s2_x3_fwd(c, f, P[name + '.conv.bias'], y, ch[l], amax_y=sl(name) if plan.h2 else None)
                 else:
-                    a[f'd{l}'] = produced(ops.conv_s2_fwd(a[f'c{l}'], W[f'pool{l}'][0], P[f'pool{l}.conv.bias'],
-                                                          g(f'd{l}', (B, hs[l], ws[l], ch[l])), ch[l]), f'pool{l}', fused=False)
-                xin = a[f'd{l}']
+                    ops.conv_s2_fwd(c, f, P[name + '.conv.bias'], y, ch[l])
+                xin = a[f'd{l}'] = T.put(y, name, fused=plan[name].fwd != 'direct')
         cur = a['c5']
         for i in range(6, 10):
             lv = 9 - i
             shp = (B, hs[lv], ws[lv], ch[lv])
-            if f'upv{i}' in self.WM:
-                u = produced(ops.convt_h2_fwd(cur, fslot(cur, f'in_upv{i}'), self.WM[f'upv{i}'][0], self.WS[f'upv{i}'], P[f'upv{i}.bias'], g(f'u{i}', shp), ch[lv],
-                                              amax_y=sl(f'upv{i}')), f'upv{i}', fused=True)
-            elif f'upv{i}' in self.WX:
-                u = produced(ops.convt_x3_fwd(cur, self.WX[f'upv{i}'][0], P[f'upv{i}.bias'], g(f'u{i}', shp), ch[lv],
-                                              amax_y=sl(f'upv{i}') if h2_on else None), f'upv{i}', fused=True)
-            else:
-                u = produced(ops.convt_fwd(cur, W[f'upv{i}'][0], P[f'upv{i}.bias'], g(f'u{i}', shp), ch[lv]), f'upv{i}', fused=False)
+            u = a[f'u{i}'] = self._convt_fwd(plan, f'upv{i}', T, cur, P[f'upv{i}.bias'], g(f'u{i}', shp), ch[lv])
             skip = a[f'c{lv + 1}']
-            a[f'u{i}'] = u
             a[f't{i}'] = cf(f'b{i}_0', u, skip, None, g(f't{i}', shp), ch[lv], RELU)
-            if f'sc{i}' in self.WM:
-                sc = ops.conv1x1_h2_fwd(u, fslot(u, f'upv{i}'), skip, fslot(skip, f'c{lv + 1}'), self.WM[f'sc{i}'][0], self.WS[f'sc{i}'], None, g(f'sc{i}', shp), ch[lv], 0)
-            elif self.WX.get(f'sc{i}', (None, None))[0] is not None:
-                sc = ops.conv1x1_x3_fwd(u, skip, self.WX[f'sc{i}'][0], None, g(f'sc{i}', shp), ch[lv], 0)
+            f, _, wslot = self._wp[f'sc{i}']
+            sc = g(f'sc{i}', shp)
+            if plan[f'sc{i}'].fwd == 'h2':
+                ops.conv1x1_h2_fwd(u, T.of(u), skip, T.of(skip), f, wslot, None, sc, ch[lv], 0)
+            elif plan[f'sc{i}'].fwd == 'x3':
+                ops.conv1x1_x3_fwd(u, skip, f, None, sc, ch[lv], 0)
             else:
-                sc = ops.conv_fwd(u, skip, W[f'sc{i}'][0], None, g(f'sc{i}', shp), ch[lv], 1, 0)
-            a[f'c{i}'] = cf(f'b{i}_1', a[f't{i}'], None, None, g(f'c{i}', shp), ch[lv], 0, residual=sc)
-            cur = a[f'c{i}']
+                ops.conv_fwd(u, skip, f, None, sc, ch[lv], 1, 0)
+            a[f'c{i}'] = cur = cf(f'b{i}_1', a[f't{i}'], None, None, g(f'c{i}', shp), ch[lv], 0, residual=sc)
         out = torch.empty((B, self.cout, H, Wd), dtype=torch.float32, device=dev)
-        if self._pol.use_thin_head(ch[0], self.cout, B * H * Wd):
-            ops.head_fwd(a['c9'], P['conv10.weight'], P['conv10.bias'], out, residual=x if (self.m.res and add_residual) else None)
+        res = x if (self.m.res and add_residual) else None
+        if plan['conv10'].fwd == 'thin':
+            ops.head_fwd(a['c9'], P['conv10.weight'], P['conv10.bias'], out, residual=res)
         else:
-            o = ops.conv_fwd(a['c9'], None, W['conv10'][0], P['conv10.bias'], g('o', (B, H, Wd, self.cout)), self.cout, 1, 0)
-            ops.nhwc_to_nchw(o, out, residual=x if (self.m.res and add_residual) else None)
+            o = ops.conv_fwd(a['c9'], None, self._wp['conv10'][0], P['conv10.bias'], g('o', (B, H, Wd, self.cout)), self.cout, 1, 0)
+            ops.nhwc_to_nchw(o, out, residual=res)
         if train:
-            a['_pol'] = self._pol
-            a['_src_name'] = src_name
+            a['_plan'] = plan
+            a['_src_name'] = T.names
             self.saved = (a, (B, H, Wd, dev), gen)
         return out
 
     # ---------------------------------------------------------------- backward
     def backward(self, g_out8, need_dx=False, accumulate=False, on_ready=None):
         a, (B, H, Wd, dev), _ = self.saved
-        self._pol = a['_pol']            # the kernel families this forward ran on (effective_policy)
+        plan = self._plan = a['_plan']     # the kernel families this forward ran on
+        self._pol = plan.pol
         bufs = self.bufs[(B, H, Wd, dev)]
-        ch, W = self.ch, self.W
+        ch = self.ch
         gb = lambda n, like: bufs.get('g_' + n, like.shape, dev)
         P = dict(self.m.named_parameters())
-        G = lambda name: self.params.grad_view(name, P[name].shape)
+        G = lambda pname: self.params.grad_view(pname, P[pname].shape) if pname else None
         acc = 1 if accumulate else 0
-        wsf = bufs.get('wgrad_ws', (self._ws_floats(B, H, Wd),), dev)
+        wsf = bufs.get('wgrad_ws', (plan.ws,), dev)
 
-        def done(pname):
+        def done(name):
             if on_ready is not None:
-                on_ready(self.params.slices[pname][0])
+                on_ready(self.params.slices[self._pname(name)[0]][0])
 
         # fp16x2 family: amax slots of the gradients (zeroed per backward), the activations' slots are the forward's
-        h2_on = bool(self.WH) or bool(self.WM)       # amax-slot upkeep whenever ANY layer runs on an fp16x2 kernel
-        if h2_on:
-            bufs.slots('b', dev).zero_()
-        src_name = a.get('_src_name', {})
-        slf = lambda t: bufs.slot('f', src_name[id(t)], dev)
-        gname = {}
-        gslot = lambda t: bufs.slot('b', gname[id(t)], dev)
-        bslot = lambda n: bufs.slot('b', n, dev) if h2_on else None
+        F = _Slots(bufs, 'f', dev, False, names=a['_src_name'])
+        T = _Slots(bufs, 'b', dev, plan.h2)
+        bslot = lambda n: T.slot(n) if plan.h2 else None
 
-        def gproduced(t, name, fused):
-            gname[id(t)] = name
-            if h2_on and not fused:
-                ops.amax(t, bufs.slot('b', name, dev))
-            return t
+        dg = lambda name, gsrc, dx1, **kw: self._conv3_dgrad(plan, name, a, F, T, gsrc, dx1, **kw)
 
-        def bneed(t, name):                        # the amax slot of a gradient an fp16x2 kernel is about to split (filled here if it is stale / missing)
-            if id(t) not in gname:
-                gproduced(t, name, fused=False)
-            return gslot(t)
-
-        def dg(name, gsrc, dx1, **kw):
-            hp = self.WH.get(name, (None, None))[1]
-            dx2 = kw.get('dx2')
-            if hp is None:
-                self._dg(name, gsrc, dx1, **kw)
-                gproduced(dx1, 'd1:' + name, fused=False)
-                if dx2 is not None:
-                    gproduced(dx2, 'd2:' + name, fused=False)
-                return
-            for k_mask, k_bits in (('mask1', 'bits1'), ('mask2', 'bits2')):      # act' masks as the forward kernels' sign bits
-                m = kw.get(k_mask)
-                if m is not None and ('bits:' + src_name.get(id(m), '?')) in a:
-                    kw[k_bits] = a['bits:' + src_name[id(m)]]
-                    kw[k_mask] = None
-            gname[id(dx1)] = 'd1:' + name
-            if dx2 is not None:
-                gname[id(dx2)] = 'd2:' + name
-            ops.conv_h2_bwd_data(gsrc, gslot(gsrc), hp, self.WS[name], dx1, amax_dx1=gslot(dx1), amax_dx2=gslot(dx2) if dx2 is not None else None, **kw)
-
-        def wgrad(pname, gpre, cout, x1, c1, x2=None, taps=9, bias=None):
-            c2 = x2.shape[3] if x2 is not None else 0
-            if (taps == 9 and h2_on and self._pol.h2_wgrad and id(gpre) in gname and id(x1) in src_name and (x2 is None or id(x2) in src_name) and
-                    self._pol.use_x3_wgrad(gpre.shape[1], gpre.shape[2], cout, c1, c2, batch=gpre.shape[0],
-                                           cs=max(gpre.shape[3], x1.shape[3], x2.shape[3] if x2 is not None else 0))):
-                ops.conv_h2_bwd_weight(gpre, gslot(gpre), cout, x1, slf(x1), c1, x2, slf(x2) if x2 is not None else None,
-                                       G(pname), G(bias) if bias else None, wsf, accumulate=acc)
-                return
-            if taps == 9 and self._pol.use_x3_wgrad(gpre.shape[1], gpre.shape[2], cout, c1, c2, batch=gpre.shape[0],
-                                                    cs=max(gpre.shape[3], x1.shape[3], x2.shape[3] if x2 is not None else 0)):
-                ops.conv_x3_bwd_weight(gpre, cout, x1, c1, x2, G(pname), G(bias) if bias else None, wsf, accumulate=acc)
-            elif taps == 9 and self._pol.use_wino_wgrad(gpre.shape[1], gpre.shape[2], cout, c1, c2, gpre.shape[3], x1.shape[3]):
-                ops.conv_wino_bwd_weight(gpre, cout, x1, c1, x2, G(pname), G(bias) if bias else None, wsf, accumulate=acc)
-            elif (taps == 1 and h2_on and self._pol.h2_pointwise and self._pol.x3 and not self._pol.use_x3g_wgrad(ops.X3G_PW, cout, c1 + c2, gpre.shape[0], gpre.shape[1],
-                                                                                                                    gpre.shape[2], gpre.shape[1], gpre.shape[2], max(gpre.shape[3], x1.shape[3], x2.shape[3] if x2 is not None else 0))
-                  and ops.h2g_wgrad_supported(ops.X3G_PW, cout, c1 + c2) and id(gpre) in gname and id(x1) in src_name and (x2 is None or id(x2) in src_name)
-                  and ops.x3_wgrad_fits(gpre.shape[0], gpre.shape[1], gpre.shape[2], max(gpre.shape[3], x1.shape[3], x2.shape[3] if x2 is not None else 0))
-                  and wsf.numel() >= ops.h2g_wgrad_workspace_floats(ops.X3G_PW, gpre.shape[0], gpre.shape[1], gpre.shape[2], cout, c1 + c2)):
-                # a shape only the fp16x2 kernel has a tile for (sc9: 32 x 64, round 6; it ran on the fp32-MFMA kernel)
-                ops.conv1x1_h2_bwd_weight(gpre, gslot(gpre), cout, x1, slf(x1), c1, x2, slf(x2) if x2 is not None else None, G(pname), G(bias) if bias else None,
-                                          wsf, accumulate=acc)
-            elif taps == 1 and self._pol.use_x3g_wgrad(ops.X3G_PW, cout, c1 + c2, gpre.shape[0], gpre.shape[1], gpre.shape[2], gpre.shape[1], gpre.shape[2],
-                                                       max(gpre.shape[3], x1.shape[3], x2.shape[3] if x2 is not None else 0)):
-                if h2_on and self._pol.h2_pointwise and id(gpre) in gname and id(x1) in src_name and (x2 is None or id(x2) in src_name):
-                    ops.conv1x1_h2_bwd_weight(gpre, gslot(gpre), cout, x1, slf(x1), c1, x2, slf(x2) if x2 is not None else None, G(pname), G(bias) if bias else None,
-                                              wsf, accumulate=acc)
-                else:
-                    ops.conv1x1_x3_bwd_weight(gpre, cout, x1, c1, x2, G(pname), G(bias) if bias else None, wsf, accumulate=acc)
-            else:
-                ops.conv_bwd_weight(gpre, cout, x1, c1, x2, G(pname), G(bias) if bias else None, taps, wsf, accumulate=acc)
+        def wgrad(name, gpre, cout, x1, c1, x2=None):
+            pw, pb = self._pname(name)
+            self._wgrad(plan[name].wgrad, F, T, gpre, cout, x1, c1, x2, G(pw), G(pb), wsf, acc, P[pw].shape[-1] ** 2)
 
         # head
         g = gb('c9', a['c9'])
-        if self._pol.use_thin_head(ch[0], self.cout, B * H * Wd):
+        if plan['conv10'].dgrad == 'thin':
             ops.head_bwd(g_out8, a['c9'], P['conv10.weight'], g, G('conv10.weight'), G('conv10.bias'), wsf, mode=0, accumulate=acc, amax_gx=bslot('head'))
-            gproduced(g, 'head', fused=True)
         else:
-            wgrad('conv10.weight', g_out8, self.cout, a['c9'], ch[0], taps=1, bias='conv10.bias')
-            ops.conv_bwd_data(g_out8, W['conv10'][1], g, taps=1)
-            gproduced(g, 'head', fused=False)
-        done('conv10.weight')
+            wgrad('conv10', g_out8, self.cout, a['c9'], ch[0])
+            ops.conv_bwd_data(g_out8, self._wp['conv10'][1], g, taps=1)
+        T.put(g, 'head', fused=plan['conv10'].dgrad == 'thin')
+        done('conv10')
         for i in range(9, 5, -1):                    # decoder blocks, top-down
             lv = 9 - i
             u, skip, t = a[f'u{i}'], a[f'c{lv + 1}'], a[f't{i}']
-            wgrad(f'conv{i}.short_cut.0.conv.conv.weight', g, ch[lv], u, ch[lv], x2=skip, taps=1)
-            wgrad(f'conv{i}.block.1.conv.conv.weight', g, ch[lv], t, ch[lv])
+            wgrad(f'sc{i}', g, ch[lv], u, ch[lv], x2=skip)
+            wgrad(f'b{i}_1', g, ch[lv], t, ch[lv])
             g_t = gb(f't{i}', t)
             dg(f'b{i}_1', g, g_t, mask1=t, mode1=RELU)
-            wgrad(f'conv{i}.block.0.conv.conv.weight', g_t, ch[lv], u, ch[lv], x2=skip)
-            done(f'conv{i}.block.0.conv.conv.weight')
+            wgrad(f'b{i}_0', g_t, ch[lv], u, ch[lv], x2=skip)
+            done(f'b{i}_0')
             g_u, g_skip = gb(f'u{i}', u), gb(f'c{lv + 1}', skip)
             dg(f'b{i}_0', g_t, g_u, dx2=g_skip)
-            # (the shortcut's gradient is ACCUMULATED into g_u and g_skip next: their slots are stale from here on -- no fp16x2 kernel reads
-            #  them before ConvTranspose2d's backward / the stride-2 backward rewrite or finish them)
-            gname.pop(id(g_u), None); gname.pop(id(g_skip), None)
-            if f'sc{i}' in self.WM:
-                # (g_u now holds block gradient + shortcut gradient: the kernel reports max |sum| -- its slot is valid again; g_skip's stays stale)
-                ops.conv1x1_h2_bwd_data(g, bneed(g, f'gc{i}'), self.WM[f'sc{i}'][1], self.WS[f'sc{i}'], g_u, accum1=1, amax_dx1=bslot(f'gu{i}'), dx2=g_skip, accum2=1)
-                gname[id(g_u)] = f'gu{i}'
-            elif self.WX.get(f'sc{i}', (None, None))[0] is not None:
-                ops.conv1x1_x3_bwd_data(g, self.WX[f'sc{i}'][1], g_u, accum1=1, dx2=g_skip, accum2=1)
+            # the shortcut's gradient is ACCUMULATED into g_u and g_skip next: their slots are stale from here on.  An fp16x2 shortcut
+            # reports max |block + shortcut gradient| of g_u (the plan runs ConvTranspose2d's backward on fp16x2 only then); g_skip's stays stale
+            T.names.pop(id(g_u), None); T.names.pop(id(g_skip), None)
+            _, d, wslot = self._wp[f'sc{i}']
+            if plan[f'sc{i}'].dgrad == 'h2':
+                ops.conv1x1_h2_bwd_data(g, T.of(g), d, wslot, g_u, accum1=1, amax_dx1=bslot(f'gu{i}'), dx2=g_skip, accum2=1)
+                T.put(g_u, f'gu{i}', fused=True)
+            elif plan[f'sc{i}'].dgrad == 'x3':
+                ops.conv1x1_x3_bwd_data(g, d, g_u, accum1=1, dx2=g_skip, accum2=1)
             else:
-                ops.conv_bwd_data(g, W[f'sc{i}'][1], g_u, accum1=1, dx2=g_skip, accum2=1, taps=1)
+                ops.conv_bwd_data(g, d, g_u, accum1=1, dx2=g_skip, accum2=1, taps=1)
             below = a['c5'] if i == 6 else a[f'c{i - 1}']
-            ct_wgrad = ops.convt_x3_bwd_weight if self._pol.use_x3g_wgrad(ops.X3G_CT, below.shape[3], g_u.shape[3], B, below.shape[1], below.shape[2],
-                                                                           g_u.shape[1], g_u.shape[2], max(below.shape[3], g_u.shape[3])) else ops.convt_bwd_weight
-            if ct_wgrad is ops.convt_x3_bwd_weight and h2_on and self._pol.h2_pointwise and id(below) in src_name and id(g_u) in gname:
-                ops.convt_h2_bwd_weight(below, slf(below), g_u, gslot(g_u), G(f'upv{i}.weight'), wsf, accumulate=acc, dbias=G(f'upv{i}.bias'))
-            else:
-                ct_wgrad(below, g_u, G(f'upv{i}.weight'), wsf, accumulate=acc, dbias=G(f'upv{i}.bias'))
-            done(f'upv{i}.weight')
-            g = gb('c5' if i == 6 else f'c{i - 1}', below)
-            if f'upv{i}' in self.WM:
-                ops.convt_h2_bwd_data(g_u, bneed(g_u, f'gu{i}'), self.WM[f'upv{i}'][1], self.WS[f'upv{i}'], g, amax_dx=bslot(f'upv{i}'))
-                gproduced(g, f'upv{i}', fused=True)
-            elif f'upv{i}' in self.WX:
-                ops.convt_x3_bwd_data(g_u, self.WX[f'upv{i}'][1], g, amax_dx=bslot(f'upv{i}'))
-                gproduced(g, f'upv{i}', fused=True)
-            else:
-                ops.convt_bwd_data(g_u, W[f'upv{i}'][1], g)
-                gproduced(g, f'upv{i}', fused=False)
+            name = f'upv{i}'
+            self._convt_wgrad(plan, name, F, T, below, g_u, G(name + '.weight'), G(name + '.bias'), wsf, acc)
+            done(name)
+            g = self._convt_dgrad(plan, name, T, g_u, gb('c5' if i == 6 else f'c{i - 1}', below))
         for l in range(5, 0, -1):                    # encoder blocks, bottom-up; g = dL/d c_l
             lv = l - 1
             t = a[f't{l}']
             xin = a['t0'] if l == 1 else a[f'd{l - 1}']
-            wgrad(f'conv{l}.block.1.conv.conv.weight', g, ch[lv], t, ch[lv])
+            wgrad(f'b{l}_1', g, ch[lv], t, ch[lv])
             g_t = gb(f't{l}', t)
             dg(f'b{l}_1', g, g_t, mask1=t, mode1=RELU)
-            wgrad(f'conv{l}.block.0.conv.conv.weight', g_t, ch[lv], xin, ch[lv])
-            done(f'conv{l}.block.0.conv.conv.weight')
+            wgrad(f'b{l}_0', g_t, ch[lv], xin, ch[lv])
+            done(f'b{l}_0')
             g_x = gb('t0' if l == 1 else f'd{l - 1}', xin)
             # identity shortcut: d/d(xin) = dgrad(block) + g ; xin = t0 is a ReLU output (mask), d_l is not
-            ud = self.WU.get(f'b{l}_0', (None, None))[1]
-            x3d = self.WX.get(f'b{l}_0', (None, None))[1]
-            h2d = self.WH.get(f'b{l}_0', (None, None))[1]
-            if h2d is not None:
-                ops.conv_h2_bwd_data_res(g_t, gslot(g_t), h2d, self.WS[f'b{l}_0'], g_x, addsrc=g, mask=xin if l == 1 else None, mode=RELU, amax_dx=bslot(f'gx{l}'))
-                gname[id(g_x)] = f'gx{l}'                          # (the stride-2 layer's fp16x2 backward kernels split it next)
-            elif x3d is not None:
-                ops.conv_x3_bwd_data_res(g_t, x3d, g_x, addsrc=g, mask=xin if l == 1 else None, mode=RELU)
-            elif ud is not None:
-                ops.conv_wino_bwd_data_res(g_t, ud, g_x, addsrc=g, mask=xin if l == 1 else None, mode=RELU)
+            _, d, wslot = self._wp[f'b{l}_0']
+            fam, mask = plan[f'b{l}_0'].dgrad, xin if l == 1 else None
+            if fam == 'h2+res':                          # (the stride-2 layer's fp16x2 backward kernels split g_x next)
+                ops.conv_h2_bwd_data_res(g_t, T.of(g_t), d, wslot, g_x, addsrc=g, mask=mask, mode=RELU, amax_dx=bslot(f'gx{l}'))
+                T.put(g_x, f'gx{l}', fused=True)
+            elif fam == 'x3+res':
+                ops.conv_x3_bwd_data_res(g_t, d, g_x, addsrc=g, mask=mask, mode=RELU)
+            elif fam == 'wino+res':
+                ops.conv_wino_bwd_data_res(g_t, d, g_x, addsrc=g, mask=mask, mode=RELU)
             else:
-                ops.conv_bwd_data_res(g_t, W[f'b{l}_0'][1], g_x, addsrc=g, mask=xin if l == 1 else None, mode=RELU)
+                ops.conv_bwd_data_res(g_t, d, g_x, addsrc=g, mask=mask, mode=RELU)
             if l > 1:
-                c_prev = a[f'c{l - 1}']
-                s2_wgrad = ops.conv_s2_x3_bwd_weight if self._pol.use_x3g_wgrad(ops.X3G_S2, g_x.shape[3], c_prev.shape[3], B, g_x.shape[1], g_x.shape[2],
-                                                                                c_prev.shape[1], c_prev.shape[2], max(g_x.shape[3], c_prev.shape[3])) else ops.conv_s2_bwd_weight
-                h2g_ok = (h2_on and self._pol.h2_pointwise and self._pol.x3 and id(c_prev) in src_name and ops.h2g_wgrad_supported(ops.X3G_S2, g_x.shape[3], c_prev.shape[3])
-                          and ops.x3_wgrad_fits(B, g_x.shape[1], g_x.shape[2], max(g_x.shape[3], c_prev.shape[3])) and ops.x3_wgrad_fits(B, c_prev.shape[1], c_prev.shape[2], max(g_x.shape[3], c_prev.shape[3])))
-                if h2g_ok:                                           # (the fp16x2 kernel also has a tile for Cout = 64: pool1, which bf16x3 left to the fp32-MFMA kernel)
-                    ops.conv_s2_h2_bwd_weight(g_x, bneed(g_x, f'gx{l}'), c_prev, slf(c_prev), G(f'pool{l - 1}.conv.weight'), G(f'pool{l - 1}.conv.bias'), wsf, accumulate=acc)
+                name, c_prev = f'pool{l - 1}', a[f'c{l - 1}']
+                s = plan[name]
+                # without a fused amax in g_x, a launch of its own fills its slot before the first fp16x2 kernel that splits it
+                fill = fam != 'h2+res'
+                if s.wgrad == 'h2':
+                    if fill:
+                        T.put(g_x, f'gx{l}', fused=False)
+                    ops.conv_s2_h2_bwd_weight(g_x, T.of(g_x), c_prev, F.of(c_prev), G(name + '.conv.weight'), G(name + '.conv.bias'), wsf, accumulate=acc)
+                elif s.wgrad == 'x3':       # (the fp16x2 kernel also has a tile for Cout = 64: pool1, which bf16x3 leaves to the fp32-MFMA kernel)
+                    ops.conv_s2_x3_bwd_weight(g_x, c_prev, G(name + '.conv.weight'), G(name + '.conv.bias'), wsf, accumulate=acc)
                 else:
-                    s2_wgrad(g_x, c_prev, G(f'pool{l - 1}.conv.weight'), G(f'pool{l - 1}.conv.bias'), wsf, accumulate=acc)
-                done(f'pool{l - 1}.conv.weight')
+                    ops.conv_s2_bwd_weight(g_x, c_prev, G(name + '.conv.weight'), G(name + '.conv.bias'), wsf, accumulate=acc)
+                done(name)
                 g = gb(f'c{l - 1}', c_prev)                          # already holds the skip gradient
-                if f'pool{l - 1}' in self.WM:
-                    ops.conv_s2_h2_bwd_data(g_x, bneed(g_x, f'gx{l}'), self.WM[f'pool{l - 1}'][1], self.WS[f'pool{l - 1}'], g, accum=1, amax_dx=bslot(f'pool{l - 1}'))
-                    gproduced(g, f'pool{l - 1}', fused=True)
-                elif f'pool{l - 1}' in self.WX:
-                    ops.conv_s2_x3_bwd_data(g_x, self.WX[f'pool{l - 1}'][1], g, accum=1, amax_dx=bslot(f'pool{l - 1}'))
-                    gproduced(g, f'pool{l - 1}', fused=True)           # (the sums it stored: skip gradient + this layer's)
+                _, d, wslot = self._wp[name]
+                if s.dgrad == 'h2':
+                    if fill and s.wgrad != 'h2':
+                        T.put(g_x, f'gx{l}', fused=False)
+                    ops.conv_s2_h2_bwd_data(g_x, T.of(g_x), d, wslot, g, accum=1, amax_dx=bslot(name))
+                elif s.dgrad == 'x3':
+                    ops.conv_s2_x3_bwd_data(g_x, d, g, accum=1, amax_dx=bslot(name))   # (the sums it stored: skip gradient + this layer's)
                 else:
-                    ops.conv_s2_bwd_data(g_x, W[f'pool{l - 1}'][1], g, accum=1)
-                    gproduced(g, f'pool{l - 1}', fused=False)
+                    ops.conv_s2_bwd_data(g_x, d, g, accum=1)
+                T.put(g, name, fused=s.dgrad != 'direct')
             else:
-                if self._pol.use_thin_first(self.cin, ch[0], H, Wd, a['x8'].shape[3]):
-                    ops.first_bwd_weight(g_x, ch[0], a['x8'], self.cin, G('conv_in.weight'), G('conv_in.bias'), wsf, accumulate=acc)
-                else:
-                    wgrad('conv_in.weight', g_x, ch[0], a['x8'], self.cin, bias='conv_in.bias')
-                done('conv_in.weight')
+                wgrad('conv_in', g_x, ch[0], a['x8'], self.cin)
+                done('conv_in')
         if need_dx:
             raise PnnpError('gradient w.r.t. the network input is not implemented on the HIP path')
         return None
-
-    def _ws_floats(self, B, H, W):
-        ch = self.ch
-        need = 1024 * max(ch)
-        for lv in range(5):
-            h, w, c = H >> lv, W >> lv, ch[lv]
-            need = max(need, ops.wino_wgrad_workspace_floats(B, h, w, c, c), ops.wino_wgrad_workspace_floats(B, h, w, c, 2 * c),
-                       ops.x3_wgrad_workspace_floats(B, h, w, c, c), ops.x3_wgrad_workspace_floats(B, h, w, c, 2 * c))
-            need = max(need, ops.wgrad_workspace_floats(B, h, w, c, c, 9), ops.wgrad_workspace_floats(B, h, w, c, 2 * c, 9),
-                       ops.wgrad_workspace_floats(B, h, w, c, 2 * c, 1), ops.wgrad_workspace_floats(B, h, w, c, self.cin, 9))
-            need = max(need, ops.x3g_wgrad_workspace_floats(ops.X3G_PW, B, h, w, c, 2 * c))
-            if lv < 4:
-                need = max(need, ops.wgrad_workspace_floats(B, h >> 1, w >> 1, ch[lv + 1], c, 4),
-                           ops.wgrad_workspace_floats(B, h >> 1, w >> 1, ch[lv + 1], c, 18),
-                           ops.x3g_wgrad_workspace_floats(ops.X3G_CT, B, h >> 1, w >> 1, ch[lv + 1], c),
-                           ops.x3g_wgrad_workspace_floats(ops.X3G_S2, B, h >> 1, w >> 1, ch[lv + 1], c),
-                           ops.h2g_wgrad_workspace_floats(ops.X3G_S2, B, h >> 1, w >> 1, ch[lv + 1], c))
-        need = max(need, ops.head_bwd_workspace_floats(ch[0]), ops.first_wgrad_workspace_floats(ch[0]))
-        return max(need, ops.wgrad_workspace_floats(B, H, W, self.cout, ch[0], 1))
 
 
 class _ResUnetFn(torch.autograd.Function):
