@@ -586,6 +586,39 @@ int pnnp_eval_post_f32(const float* net_out, const float* lr_in, float* dn, floa
 int pnnp_psnr_ssim_f32(const float* a, const float* b, float* out2 /* {psnr, ssim} */, int C, int H, int W,
                        double* workspace /* >= 2*C*ceil(H/32)*ceil(W/32) doubles */, void* stream);
 
+/* ---------------------------------------------------------------- range census of the fp16x2 family (csrc/range_census.hip)
+ * Per job (a tensor an fp16x2 kernel split and the amax slot it took the scale from): an integer histogram of
+ * k = floor(log2 A) - floor(log2 |x|) over the finite non-zero elements (A: the float whose bits the slot holds; bins 0 .. 46, bin 47 = k >= 47)
+ * and the counters zero, nonfinite and over (|x| > A: the slot contract says never).  The split keeps max(0, min(22, 39 - k)) significand
+ * bits of an element in bin k.  `table` (device, 16-byte aligned, pnnp_census_table_words(rows) words, zeroed by the caller, word 0 = the first
+ * "low-bit" bin) holds one row of PNNP_CENSUS_ROW_WORDS per job `row`: the running counters since the caller last zeroed the table, the
+ * largest per-census low-bit share (share of the finite non-zero elements in bins >= word 0, as float bits) with the `step` of that census, the
+ * latest share, the slot's bits and the number of censuses; words PNNP_CENSUS_SCRATCH .. of a row are the census's own 32-bit counts (zero
+ * between launches).  `jobs`: a DEVICE array (16-byte aligned) of `njobs` <= PNNP_CENSUS_MAX_JOBS jobs with distinct rows, `x` 16-byte aligned,
+ * n < 2^32.  Two launches (count, then summary); integer atomics only, so the table is bitwise reproducible. */
+#define PNNP_CENSUS_BINS 48
+#define PNNP_CENSUS_ZERO 48
+#define PNNP_CENSUS_NONFINITE 49
+#define PNNP_CENSUS_OVER 50
+#define PNNP_CENSUS_COUNTERS 51         /* words 0 .. 50 of a row: bins, zero, nonfinite, over */
+#define PNNP_CENSUS_WORST 51            /* float bits of the largest per-census low-bit share */
+#define PNNP_CENSUS_WORST_STEP 52
+#define PNNP_CENSUS_LAST 53             /* float bits of the latest census's share */
+#define PNNP_CENSUS_AMAX 54             /* the slot's bits at the latest census */
+#define PNNP_CENSUS_CENSUSES 55
+#define PNNP_CENSUS_SCRATCH 64
+#define PNNP_CENSUS_ROW_WORDS 128
+#define PNNP_CENSUS_HDR_WORDS 64        /* header: [0] first low-bit bin (set by the caller), [1] censuses run, [2] step of the latest */
+#define PNNP_CENSUS_MAX_JOBS 512
+typedef struct PnnpCensusJob {
+    const float* x; int64_t n;          /* the tensor's elements */
+    const unsigned* slot;               /* its amax slot */
+    int row, reserved;                  /* output row of the table; reserved = 0 */
+} PnnpCensusJob;
+int pnnp_census_job_bytes(void);
+int64_t pnnp_census_table_words(int rows);
+int pnnp_range_census_f32(const PnnpCensusJob* jobs /*[device]*/, int njobs, uint64_t* table, long long step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,15 @@ class PnnpError(RuntimeError):
     pass
 
 
+class PnnpRangeError(PnnpError):
+    """A range census tripped (HipTrainStep.check_range with on_range_trip='raise'): some tensor's per-tensor fp16x2 scale cost its small
+    elements their float32-level accuracy, or a tensor held inf / NaN, or exceeded its amax slot."""
+
+
+class PnnpRangeWarning(UserWarning):
+    """A range census tripped (HipTrainStep.check_range with on_range_trip='warn' or 'fallback')."""
+
+
 def lib():
     """Load libpnnp_hip.so (built in-tree by ``__graft_entry__.build()``)."""
     global _lib

@@ -159,7 +159,8 @@ class ResUnetEngine(_EngineBase):
         a['x8'] = ops.nchw_to_nhwc(x, g('x8', (B, H, Wd, self.cin_pad)), self.cin_pad, reflect_pad=reflect_pad)
         # fp16x2 family (csrc/h2.h): amax slots of the activations, keyed by the layer that wrote the tensor; sign bits of the ReLU outputs
         # that backward-data will need as masks
-        T = _Slots(bufs, 'f', dev, plan.h2)
+        split = {} if train else None                                 # (range census) what the fp16x2 kernels split in this step
+        T = _Slots(bufs, 'f', dev, plan.h2, log=split)
         sl = T.slot
 
         def cf(name, src, src2, bias, out, cout, act, residual=None):
@@ -219,6 +220,7 @@ class ResUnetEngine(_EngineBase):
         if train:
             a['_plan'] = plan
             a['_src_name'] = T.names
+            a['_split'] = split
             self.saved = (a, (B, H, Wd, dev), gen)
         return out
 
@@ -240,8 +242,8 @@ class ResUnetEngine(_EngineBase):
                 on_ready(self.params.slices[self._pname(name)[0]][0])
 
         # fp16x2 family: amax slots of the gradients (zeroed per backward), the activations' slots are the forward's
-        F = _Slots(bufs, 'f', dev, False, names=a['_src_name'])
-        T = _Slots(bufs, 'b', dev, plan.h2)
+        F = _Slots(bufs, 'f', dev, False, names=a['_src_name'], log=a['_split'])
+        T = _Slots(bufs, 'b', dev, plan.h2, log=a['_split'])
         bslot = lambda n: T.slot(n) if plan.h2 else None
 
         dg = lambda name, gsrc, dx1, **kw: self._conv3_dgrad(plan, name, a, F, T, gsrc, dx1, **kw)

@@ -125,6 +125,41 @@ class _EngineBase:
                 add(k, 'grad', t)
         return rows
 
+    def census_pairs(self):
+        """(name, kind, tensor, amax slot) of every tensor an fp16x2 kernel split in the saved training step: what _Slots.of handed to the h2
+        kernels of the forward and backward (kind 'act': table 'f', named as in the saved activations; 'grad': table 'b', named by buffer) and
+        the weights the fp16x2 packs split against their PackJobs slots ('weight').  Empty under a policy without fp16x2 kernels."""
+        if self.saved is None:
+            raise PnnpError('range census: no saved training forward (run it after a training forward and backward)')
+        a, key, _ = self.saved
+        bufs, dev = self.bufs[key], key[3]
+        act = {id(t): k for k, t in a.items() if torch.is_tensor(t) and not k.startswith(('bits:', 'pc', '_'))}
+        grad = {id(t): k for k, t in bufs.t.items() if torch.is_tensor(t)}
+        out, seen = [], set()
+        for (which, _, sname), t in (a.get('_split') or {}).items():
+            name = (act if which == 'f' else grad).get(id(t), sname)
+            if (which, name) in seen:                            # one buffer under two slots (the census would show it as `over`)
+                name = f'{name}@{sname}'
+            seen.add((which, name))
+            out.append((name, 'act' if which == 'f' else 'grad', t, bufs.slot(which, sname, dev)))
+        if a['_plan'].h2:
+            pname = {p.data_ptr(): n for n, p in self.m.named_parameters()}
+            for w, slot in self._jobs.split_weights:
+                out.append((pname.get(w.data_ptr(), '?'), 'weight', w, slot))
+        return out
+
+    def range_census(self, census=None, step=0):
+        """Count the saved training step's split tensors into ``census`` (an ops.RangeCensus; None: one the engine keeps) on the current
+        stream, without synchronising; returns the census.  Call it after a training forward and backward and before the optimiser moves
+        the weights (HipTrainStep does, every ``range_every`` steps).  Under a policy without fp16x2 kernels nothing is counted."""
+        pairs = self.census_pairs()
+        if census is None:
+            if getattr(self, '_census', None) is None or self._census.device != self.saved[1][3]:
+                self._census = ops.RangeCensus(self.saved[1][3])
+            census = self._census
+        census.run(pairs, step)
+        return census
+
     def mark_dirty(self):
         """Parameters were modified behind torch's back (fused Adam on the flat buffer)."""
         self._dirty_epoch += 1
@@ -174,7 +209,7 @@ class _EngineBase:
             T.names[id(dx1)] = 'd1:' + name
             if dx2 is not None:
                 T.names[id(dx2)] = 'd2:' + name
-            ops.conv_h2_bwd_data(gsrc, T.of(gsrc), d, wslot, dx1, amax_dx1=T.of(dx1), amax_dx2=T.of(dx2) if dx2 is not None else None, **kw)
+            ops.conv_h2_bwd_data(gsrc, T.of(gsrc), d, wslot, dx1, amax_dx1=T.slot('d1:' + name), amax_dx2=T.slot('d2:' + name) if dx2 is not None else None, **kw)
             return
         if fam == 'x3':
             ops.conv_x3_bwd_data(gsrc, d, dx1, **kw)
@@ -238,9 +273,10 @@ class _Slots:
     zeroed when a backward starts).  ``put`` records which slot a tensor's amax is in -- its producer wrote it (fused) or, when ``on``
     (some layer of the plan runs on an fp16x2 kernel), a standalone amax launch fills it here."""
 
-    def __init__(self, bufs, which, dev, on, names=None):
+    def __init__(self, bufs, which, dev, on, names=None, log=None):
         self.bufs, self.which, self.dev, self.on = bufs, which, dev, on
         self.names = {} if names is None else names          # id(tensor) -> slot name
+        self.log = log                                       # a training step's split operands for the range census (None: not recorded)
         if on:
             bufs.slots(which, dev).zero_()
 
@@ -254,7 +290,12 @@ class _Slots:
         return t
 
     def of(self, t):
-        return self.slot(self.names[id(t)])
+        """The slot of ``t`` for an fp16x2 kernel that splits ``t`` (every caller hands it to one as an operand's amax); recorded for the range
+        census (_EngineBase.census_pairs)."""
+        name = self.names[id(t)]
+        if self.log is not None:
+            self.log[(self.which, id(t), name)] = t
+        return self.slot(name)
 
 
 class FlatParams:
@@ -460,7 +501,8 @@ class UNetEngine(_EngineBase):
         a = {}
         # fp16x2 family: amax slots of the activations (keyed by the name of the layer that wrote the tensor; a pooled map shares its
         # full-resolution map's slot) and, in a training forward, the sign bits of every LeakyReLU output that backward-data will need
-        T = _Slots(bufs, 'f', dev, plan.h2)
+        split = {} if train else None                                 # (range census) what the fp16x2 kernels split in this step
+        T = _Slots(bufs, 'f', dev, plan.h2, log=split)
         sl = T.slot
         # the zero-padded NHWC copy of the network input; its amax rides on the layout pass when conv1_1 runs on the fp16x2 kernel
         first_h2 = plan['conv1_1'].fwd == 'h2'
@@ -546,6 +588,7 @@ class UNetEngine(_EngineBase):
         if train:
             a['_plan'] = plan
             a['_src_name'] = T.names
+            a['_split'] = split
             self.saved = (a, (B, H, W, dev), gen)
         return out
 
@@ -566,8 +609,8 @@ class UNetEngine(_EngineBase):
         acc = 1 if accumulate else 0
         wsf = bufs.get('wgrad_ws', (plan.ws,), dev)
         # fp16x2 family: amax slots of the gradients (keyed by the buffer name), zeroed per backward; the activations' slots are the forward's
-        F = _Slots(bufs, 'f', dev, False, names=a['_src_name'])
-        T = _Slots(bufs, 'b', dev, plan.h2)
+        F = _Slots(bufs, 'f', dev, False, names=a['_src_name'], log=a['_split'])
+        T = _Slots(bufs, 'b', dev, plan.h2, log=a['_split'])
 
         dgrad = lambda name, gsrc, dx1, **kw: self._conv3_dgrad(plan, name, a, F, T, gsrc, dx1, **kw)
 

@@ -2,6 +2,7 @@
 fp32; activations NHWC.  No CPU path: every function raises on CPU tensors."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -56,6 +57,10 @@ def _prep():
         L.pnnp_h2g_wgrad_workspace_floats.restype = C.c_int64
         L.pnnp_head_bwd_workspace_floats.restype = C.c_int64
         L.pnnp_first_wgrad_workspace_floats.restype = C.c_int64
+        L.pnnp_census_table_words.restype = C.c_int64
+        if L.pnnp_census_job_bytes() != C.sizeof(CensusJob):
+            raise _lib.PnnpError(f'{_lib.LIB_PATH}: PnnpCensusJob of {L.pnnp_census_job_bytes()} bytes, these bindings were written for '
+                                 f'{C.sizeof(CensusJob)}: rebuild the library (tools/build.py)')
         L._pnnp_sigs = True
     return L
 
@@ -88,6 +93,7 @@ class PackJobs:
         self.n_amax = C.c_int(0)
         self.wslots = None
         self._wslot_of = {}
+        self.split_weights = []                  # (weight tensor, its slot) for every weight an fp16x2 pack splits: the range census's weight jobs
 
     def add_conv(self, w, fwd, dgrad, cin_pad=None, cout_pad=None):
         co, ci, kh, kw = w.shape
@@ -123,6 +129,7 @@ class PackJobs:
             slot = self.wslots[i:i + 1]
             check(_prep().pnnp_pack_jobs_add_amax(self.amax_jobs, C.byref(self.n_amax), self.cap, ptr(w), C.c_int64(w.numel()), ptr(slot)), 'pack_jobs_add_amax')
             self._wslot_of[key] = slot
+            self.split_weights.append((w, slot))
             self.keep += [w]
         return self._wslot_of[key]
 
@@ -184,6 +191,150 @@ class PackJobs:
             self.wslots.zero_()
             check(_prep().pnnp_pack_jobs_f32(self.amax_jobs, self.n_amax.value, stream()), 'pack_jobs (amax)')
         check(_prep().pnnp_pack_jobs_f32(self.jobs, self.n.value, stream()), 'pack_jobs')
+
+
+
+# ---- range census of the fp16x2 family (csrc/range_census.hip, include/pnnp_hip.h PNNP_CENSUS_*)
+class CensusJob(C.Structure):                    # PnnpCensusJob of include/pnnp_hip.h
+    _fields_ = [('x', C.c_void_p), ('n', C.c_int64), ('slot', C.c_void_p), ('row', C.c_int), ('reserved', C.c_int)]
+
+
+CENSUS_BINS, CENSUS_HDR, CENSUS_ROW, CENSUS_MAX_JOBS = 48, 64, 128, 512
+_C_ZERO, _C_NONFIN, _C_OVER, _C_COUNTERS, _C_WORST, _C_WSTEP, _C_LAST, _C_AMAX, _C_NCENS = 48, 49, 50, 51, 51, 52, 53, 54, 55
+
+
+def census_bin_bits(k):
+    """Significand bits the fp16x2 split keeps of an element k binades below its tensor's amax (bin 47: k >= 47): csrc/range_census.hip."""
+    return max(0, min(22, 39 - int(k)))
+
+
+def census_first_low_bin(min_bits):
+    """The first bin whose elements keep fewer than ``min_bits`` bits (24 for 16 bits); 48: none."""
+    return next((k for k in range(CENSUS_BINS) if census_bin_bits(k) < min_bits), CENSUS_BINS)
+
+
+def _f32(bits):
+    return float(np.array([int(bits) & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
+
+
+def census_rows(table, meta, min_bits=16):
+    """The report of a census table (1-D int64 array, host): one dict per row that took part in a census since the table was reset.
+    ``log2_ratio`` is the median bin (h2_range_report's log2(amax / median |x|) to within one), ``frac_small`` the share of the finite non-zero
+    elements 18 or more binades down (h2_range_report's "below 2^-18 amax"), ``low_share`` the share in bins that keep fewer than ``min_bits``
+    bits over all censuses, ``worst_share`` / ``worst_step`` the largest per-census share and the step it was reached at."""
+    t = np.asarray(table, dtype=np.int64)
+    kmin = census_first_low_bin(min_bits)
+    rows = []
+    for r, (name, kind) in enumerate(meta):
+        w = t[CENSUS_HDR + r * CENSUS_ROW:CENSUS_HDR + (r + 1) * CENSUS_ROW]
+        if len(w) < CENSUS_ROW or w[_C_NCENS] == 0:
+            continue
+        hist = [int(v) for v in w[:CENSUS_BINS]]
+        n = sum(hist)
+        med = float('nan')
+        if n:
+            acc = 0
+            for k, v in enumerate(hist):
+                acc += v
+                if 2 * acc >= n:
+                    med = float(k)
+                    break
+        rows.append(dict(name=name, kind=kind, amax=_f32(w[_C_AMAX]), log2_ratio=med, frac_small=(sum(hist[18:]) / n if n else 0.0),
+                         low_share=(sum(hist[kmin:]) / n if n else 0.0), worst_share=_f32(w[_C_WORST]), worst_step=int(w[_C_WSTEP]),
+                         nonfinite=int(w[_C_NONFIN]), over=int(w[_C_OVER]), zero=int(w[_C_ZERO]), count=n, censuses=int(w[_C_NCENS]), hist=hist))
+    return rows
+
+
+def reduce_census_table(table, group=None):
+    """The census table summed over the ranks of ``group`` (counters: integer SUM; worst share, latest share, amax: MAX; the step of the worst
+    share: the largest step among the ranks that hold it), so every rank reads the same report.  Returns a new tensor."""
+    import torch.distributed as dist
+    rows = (table.numel() - CENSUS_HDR) // CENSUS_ROW
+    body = table[CENSUS_HDR:CENSUS_HDR + rows * CENSUS_ROW].view(rows, CENSUS_ROW)
+    sums = torch.cat([body[:, :_C_COUNTERS], body[:, _C_NCENS:_C_NCENS + 1]], 1).contiguous()
+    maxs = torch.cat([body[:, [_C_WORST, _C_LAST, _C_AMAX]], table[1:3].view(1, 2).expand(rows, 2)], 1).contiguous()
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(maxs, op=dist.ReduceOp.MAX, group=group)
+    step = torch.where(body[:, _C_WORST] == maxs[:, 0], body[:, _C_WSTEP], torch.full_like(body[:, _C_WSTEP], -1)).contiguous()
+    dist.all_reduce(step, op=dist.ReduceOp.MAX, group=group)
+    out = table.clone()
+    ob = out[CENSUS_HDR:CENSUS_HDR + rows * CENSUS_ROW].view(rows, CENSUS_ROW)
+    ob[:, :_C_COUNTERS] = sums[:, :_C_COUNTERS]
+    ob[:, _C_NCENS] = sums[:, _C_COUNTERS]
+    ob[:, _C_WORST], ob[:, _C_LAST], ob[:, _C_AMAX] = maxs[:, 0], maxs[:, 1], maxs[:, 2]
+    ob[:, _C_WSTEP] = step
+    if rows:
+        out[1:3] = maxs[0, 3:5]
+    return out
+
+
+class RangeCensus:
+    """The device table of range censuses (csrc/range_census.hip) and its job tables.  ``run(pairs, step)`` counts, on the current stream and
+    without synchronising, every (name, kind, tensor, amax slot) pair in one launch (+ a one-workgroup summary); rows are assigned per
+    (kind, name) on first sight.  The device job table of a pair set is built once (pinned host copy, asynchronous upload) and reused while
+    the same buffers come back.  ``read()`` is the one host synchronisation: the report of census_rows; ``reset()`` zeroes the table."""
+
+    def __init__(self, device, min_bits=16, rows=256):
+        self.device = torch.device(device)
+        self.min_bits = int(min_bits)
+        self.kmin = census_first_low_bin(self.min_bits)
+        self.cap = int(rows)
+        self.table = torch.zeros(int(_prep().pnnp_census_table_words(self.cap)), dtype=torch.int64, device=self.device)
+        self.meta = []                           # row -> (name, kind)
+        self._row = {}
+        self._sets = {}
+        self.reset()
+
+    def reset(self):
+        self.table.zero_()
+        self.table[0] = self.kmin
+
+    def row(self, name, kind):
+        key = (kind, name)
+        if key not in self._row:
+            if len(self.meta) >= self.cap:
+                raise _lib.PnnpError(f'range census table full ({self.cap} rows)')
+            self._row[key] = len(self.meta)
+            self.meta.append((name, kind))
+        return self._row[key]
+
+    def _jobs(self, pairs):
+        key = tuple((kind, name, t.data_ptr(), t.numel(), s.data_ptr()) for name, kind, t, s in pairs)
+        got = self._sets.get(key)
+        if got is None:
+            if len(pairs) > CENSUS_MAX_JOBS:
+                raise _lib.PnnpError(f'range census: {len(pairs)} jobs, at most {CENSUS_MAX_JOBS} per launch')
+            arr = (CensusJob * len(pairs))()
+            rows = set()
+            for i, (name, kind, t, s) in enumerate(pairs):
+                require_cuda(t, s)
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16 or t.numel() >= 1 << 32 or s.dtype != torch.int32:
+                    raise _lib.PnnpError(f'range census: {kind} {name} must be a contiguous, 16-byte aligned float32 tensor of < 2^32 elements with an int32 slot')
+                r = self.row(name, kind)
+                if r in rows:
+                    raise _lib.PnnpError(f'range census: {kind} {name} appears twice in one census')
+                rows.add(r)
+                arr[i] = CensusJob(t.data_ptr(), t.numel(), s.data_ptr(), r, 0)
+            nb = C.sizeof(arr)
+            host = torch.empty(nb, dtype=torch.uint8).pin_memory()
+            C.memmove(host.data_ptr(), arr, nb)
+            dev = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            dev.copy_(host, non_blocking=True)
+            if len(self._sets) >= 16:
+                self._sets.clear()
+            got = self._sets[key] = (dev, len(pairs), host, [p[2:] for p in pairs])
+        return got
+
+    def run(self, pairs, step=0):
+        if not pairs:
+            return
+        dev, n, _, _ = self._jobs(pairs)
+        check(_prep().pnnp_range_census_f32(ptr(dev), n, ptr(self.table), C.c_longlong(int(step)), stream()), 'range_census')
+
+    def read(self, reduce=False, group=None):
+        """The report (census_rows) -- with ``reduce``, of the table summed over the ranks of ``group`` (reduce_census_table).  Synchronises."""
+        t = reduce_census_table(self.table, group) if reduce else self.table
+        return census_rows(t.cpu().numpy(), self.meta, self.min_bits)
 
 
 def pack_convt_weight(w, fwd, dgrad):

@@ -13,12 +13,13 @@ crop index, so the noise does not depend on the number of GPUs.
 import math
 
 import os
+import warnings
 
 import numpy as np
 import torch
 
 from . import ops, process
-from ._lib import PnnpError
+from ._lib import PnnpError, PnnpRangeError, PnnpRangeWarning
 
 
 def get_cos_lr(step, period=1000, peak=20, lr=1e-4, ratio=0.2):
@@ -133,6 +134,36 @@ class BucketedAllReduce:
         return out
 
 
+RANGE_TRIP_ACTIONS = ('warn', 'raise', 'fallback')
+
+
+def range_trips(rows, max_share):
+    """The rows of a range-census report (ops.census_rows) that trip: worst per-census low-bit share above ``max_share``, any inf / NaN, or
+    any element above its amax slot."""
+    return [r for r in rows if r['worst_share'] > max_share or r['nonfinite'] > 0 or r['over'] > 0]
+
+
+def handle_range_trips(rows, max_share, on_trip, engine):
+    """Act on a range-census report: nothing when no row trips; else 'warn' (PnnpRangeWarning), 'raise' (PnnpRangeError) or 'fallback'
+    (warn, then ``engine.set_policy(h2=False)``: the exact bf16x3 split for the rest of the run).  Returns the tripped rows."""
+    if on_trip not in RANGE_TRIP_ACTIONS:
+        raise ValueError(f'on_range_trip must be one of {RANGE_TRIP_ACTIONS}, got {on_trip!r}')
+    trips = range_trips(rows, max_share)
+    if not trips:
+        return trips
+    msg = 'fp16x2 range census tripped: ' + '; '.join(
+        f"{r['kind']} {r['name']}: low-bit share {r['worst_share']:.3g} (limit {max_share:.3g}) at step {r['worst_step']}, "
+        f"nonfinite {r['nonfinite']}, over {r['over']}" for r in trips)
+    if on_trip == 'raise':
+        raise PnnpRangeError(msg)
+    if on_trip == 'fallback':
+        msg += ' -- switching the network to the bf16x3 family (set_policy(h2=False))'
+    warnings.warn(msg, PnnpRangeWarning, stacklevel=3)
+    if on_trip == 'fallback':
+        engine.set_policy(h2=False)
+    return trips
+
+
 def shard_crops(global_batch, rank, world):
     """Rank r of `world` owns crops [lo, hi) of a global batch (strong scaling); returns
     (lo, hi).  Remainders go to the low ranks."""
@@ -157,7 +188,8 @@ class HipTrainStep:
 
     def __init__(self, net, lr=1e-4, camera_type='SonyA7S2', noise_code='pr', ori=False, clip=process.HALF_CLIP,
                  seed=1997, rank=0, world=1, group=None, bucket_bytes=8 << 20, force_reducer=False, tukey=False,
-                 proxy_net=None, proxy_ratio_choices=None, proxy_iso=None, global_batch=None, overlap_allreduce=False):
+                 proxy_net=None, proxy_ratio_choices=None, proxy_iso=None, global_batch=None, overlap_allreduce=False,
+                 range_every=128, range_min_bits=16, range_max_share=1e-3, on_range_trip='warn'):
         """``proxy_net`` (a NoiseFlow, `arch_proxy` of the run files): noise comes from ``proxy_net.sample`` instead of the
         physics sampler -- the 'NF_Syn_Dataset' branch of preprocess (trainer_SID.py:463-472: ratio ~ U(100,300) per crop,
         one random legal ISO per batch) or, with ``proxy_ratio_choices`` (dst.ratio_list), the 'IMX686_NF_Syn_Dataset'
@@ -167,7 +199,17 @@ class HipTrainStep:
         [r B, (r+1) B).  An integer = strong scaling of ONE global batch over the ranks by ``shard_crops`` (remainders to the low
         ranks, so shards may differ by one crop): the rank's crops are [lo, hi) of that batch -- the sampler's counter base is
         ``lo``, and the local gradient (a mean over the rank's crops) is weighted by B_local / global_batch so that the
-        all-reduced sum is the mean over the global batch."""
+        all-reduced sum is the mean over the global batch.
+
+        Range census (csrc/range_census.hip): every ``range_every``-th step (0: never) counts, on the step's stream
+        and without a host synchronisation, how far below its amax slot every element of every tensor the fp16x2 kernels split in that step
+        lies; ``check_range()`` (one synchronisation, at epoch ends) reports it and acts on ``on_range_trip`` ('warn' / 'raise' /
+        'fallback') when a tensor's share of elements that keep fewer than ``range_min_bits`` significand bits exceeded ``range_max_share``
+        in some census, or a tensor held inf / NaN or exceeded its slot."""
+        if on_range_trip not in RANGE_TRIP_ACTIONS:
+            raise ValueError(f'on_range_trip must be one of {RANGE_TRIP_ACTIONS}, got {on_range_trip!r}')
+        self.range_every, self.range_min_bits, self.range_max_share, self.on_range_trip = int(range_every), int(range_min_bits), float(range_max_share), on_range_trip
+        self.census = None
         self.global_batch = global_batch
         self.overlap_allreduce = overlap_allreduce      # BucketedAllReduce(overlap=): buckets from inside the backward pass (see its docstring)
         # collectives resident on some CUs while convolution grids are dispatched: quarter shares handed out by the hardware dispatcher
@@ -343,6 +385,11 @@ class HipTrainStep:
         finally:
             if prev_split is not None:
                 ops.set_persistent_split(prev_split)
+        if self.range_every > 0 and (self.step_count + 1) % self.range_every == 0:
+            # every split tensor still holds what its slot describes, and Adam has not moved the weights yet
+            if self.census is None or self.census.device != dev:
+                self.census = ops.RangeCensus(dev, self.range_min_bits)
+            e.range_census(self.census, step=self.step_count + 1)
         if self.reducer is not None:
             self.reducer.finish()
         self.step_count += 1
@@ -358,6 +405,18 @@ class HipTrainStep:
         (`runfile.main` does); `make_noisy_proxy` itself checks on the first step and every ``proxy_check_every`` steps."""
         if self.proxy_net is not None and hasattr(self.proxy_net, 'check_scale_flag'):
             self.proxy_net.check_scale_flag()
+
+    def check_range(self):
+        """The range censuses since the last call (one row per tensor: ops.census_rows), summed over the ranks when ``world > 1`` so that
+        every rank decides alike; acts on ``on_range_trip`` when a row trips (range_trips) and resets the table.  One host synchronisation:
+        call it at epoch ends (`runfile.main` does, beside check_proxy).  [] when no census has run."""
+        if self.census is None:
+            return []
+        import torch.distributed as dist
+        rows = self.census.read(reduce=self.world > 1 and dist.is_initialized(), group=self.group)
+        self.census.reset()
+        handle_range_trips(rows, self.range_max_share, self.on_range_trip, self.engine)
+        return rows
 
     @staticmethod
     def psnr_from(loss_out, elems_per_crop):
