@@ -38,7 +38,7 @@ const char* pnnp_error_string(int code);
  * pnnp_pack_job_bytes() with its own sizeof(PnnpPackJob) before it passes a job table (pnnp_amd/ops.py does, on first use).
  *   6 (round 6): PnnpPackJob carries a trailing `amax` pointer since round 5 (an older caller's job ARRAY would be read with the wrong stride);
  *                pnnp_x3_supported refuses more than 1024 output channels (PNNP_E_UNSUPPORTED from the pnnp_conv3x3_x3_* entries beyond it). */
-#define PNNP_ABI_VERSION 6
+#define PNNP_ABI_VERSION 7
 int pnnp_abi_version(void);
 int pnnp_pack_job_bytes(void);
 /* Number of compute units etc. of the current device (0 on failure). */
@@ -262,6 +262,20 @@ int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_
                                  float* dx1, int C1, const float* mask1, const unsigned* bits1, int mode1, int accum1, unsigned* amax_dx1,
                                  float* dx2 /*or null*/, int C2, const float* mask2, const unsigned* bits2, int mode2, int accum2, unsigned* amax_dx2,
                                  int B, int H, int W, void* stream);
+/* A COLUMN RANGE of that layer into one destination, optionally with the backward pass of MaxPool2d(2) folded into the store (round 7).  The backward-data pack
+ * is column-block-major, so columns [col0, col0 + C) of a pack with `cols` columns (both multiples of 32, the range inside the pack: else PNNP_E_INVALID) are
+ * the same kernel on an offset pack pointer: dx [B][H][W][C] = act'(bits) x dgrad (bits null: no mask; accum as above).  A two-destination launch of
+ * pnnp_conv3x3_h2_bwd_data_f32 equals the two launches over [0, C1) and [C1, C1 + C2) bit for bit (same tiles, same sums).
+ * gp / codes given: dx is ALSO the input of a MaxPool2d(2) (archs/Unet.py: conv1_2 .. conv4_2, skip connection + pool); gp [B][H/2][W/2][gp_cs] is the pooled
+ * map's gradient (its first C channels are used; gp_cs >= C, a multiple of 4; 16-byte aligned), codes the bytes pnnp_maxpool2_fwd_codes_f32 /
+ * pnnp_conv3x3_h2_fwd_pool_f32 wrote (4-byte aligned, same geometry).  The kernel stores  act'(bits) x dgrad + unpool(gp, codes)  and raises amax_dx with
+ * max |stored value|.  BIT-EXACTNESS CONTRACT: dx and amax_dx are bit-identical to this entry without gp / codes followed by
+ * pnnp_maxpool2_bwd_codes_amax_f32(codes, gp, dx, B, H, W, C, mode, 1, amax_dx') -- the same float32 operations in the same order (t + ((k == argmax) ?
+ * g x (sign_k ? 1 : slope) : 0), the addition also where the term is zero), amax_dx == amax_dx' -- without the pass's read-modify-write of the full-resolution
+ * map.  Requires bits and mode != 0, accum == 0, even H and W; anything else returns PNNP_E_UNSUPPORTED and launches nothing. */
+int pnnp_conv3x3_h2_bwd_data_unpool_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w, int col0, int cols,
+                                        float* dx, int C, const unsigned* bits /*or null*/, int mode, int accum, unsigned* amax_dx /*or null*/,
+                                        const float* gp /*or null*/, int gp_cs, const unsigned char* codes /*or null*/, int B, int H, int W, void* stream);
 /* backward-weight: both operands are split on the fly; same workspace (pnnp_x3_wgrad_workspace_floats), supported shapes
  * (pnnp_x3_wgrad_supported, pnnp_x3_wgrad_fits) and contract as pnnp_conv3x3_x3_bwd_weight_f32 */
 int pnnp_conv3x3_h2_bwd_weight_f32(const float* g, int g_cs, int Cout, const unsigned* amax_g, const float* x1, int x1_cs, int C1, const unsigned* amax_x1,

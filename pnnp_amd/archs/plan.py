@@ -36,9 +36,17 @@ class ConvPolicy:
         self.head_fused = bool(h2) and os.environ.get('PNNP_HEAD_FUSED', '1') != '0'          # (A/B switch) conv10_1 inside conv9_2's epilogue (round 6)
         self.splitk = bool(h2) and os.environ.get('PNNP_SPLITK', '1') != '0'                  # (A/B switch) split-K forward launches for small grids (round 6)
         self.convt_bits = bool(h2) and os.environ.get('PNNP_CONVT_BITS', '1') != '0'          # (A/B switch) ConvTranspose2d backward-data masks with sign bits (round 6)
+        # (A/B switch, round 7) MaxPool2d backward inside the epilogue of the decoder's skip-gradient launch (csrc/conv_h2s.hip EK_BWDU) instead of a pass of
+        # its own; ``unpool_levels``: the encoder levels (1 = the full-resolution one .. 4) it applies to -- PNNP_UNPOOL_LEVELS=234 keeps level 1 on the pass
+        self.unpool_fused = bool(h2) and os.environ.get('PNNP_UNPOOL_FUSED', '1') != '0'
+        self.unpool_levels = tuple(sorted({int(c) for c in os.environ.get('PNNP_UNPOOL_LEVELS', '1234') if c in '1234'}))
 
     def key(self):
         return (self.wino, self.wino_wgrad, self.wino_mink, self.x3, self.thin, self.pool_fused, self.h2, self.h2_wgrad, self.h2_pointwise, self.head_fused, self.splitk, self.convt_bits)
+
+    def plan_key(self):
+        """What a cached Plan depends on: key() (the families and packs) + the switches that only change the launch sequence."""
+        return self.key() + (self.unpool_fused, self.unpool_levels)
 
     def use_thin_head(self, cin, cout, npix):
         return self.thin and ops.head_supported(cin, cout, npix)
@@ -95,10 +103,13 @@ DEFAULT_POLICY = ConvPolicy(wino=os.environ.get('PNNP_WINO', '1') != '0', x3=os.
 
 class Step:
     """What one layer runs: ``fwd`` / ``dgrad`` / ``wgrad`` families (see the module docstring) and ``pack`` = the (forward, backward-data)
-    weight packs it needs; ``ks``: K slices of a split-K forward; ``codes``: a pooled layer keeps argmax / sign codes for its backward."""
+    weight packs it needs; ``ks``: K slices of a split-K forward; ``codes``: a pooled layer keeps argmax / sign codes for its backward;
+    ``unpool`` (decoder conv{6..9}_1): its backward-data runs as two column-range launches, the skip half deferred to where the pooled map's
+    gradient exists and carrying MaxPool2d's backward in its epilogue (not a family: ``families()`` does not show it)."""
 
     def __init__(self, fwd, dgrad=None, wgrad=None, pack=None, ks=1, codes=False):
         self.fwd, self.dgrad, self.wgrad, self.ks, self.codes = fwd, dgrad, wgrad, ks, codes
+        self.unpool = False
         self.pack = pack if pack is not None else (fwd, dgrad)
 
     def families(self):
@@ -193,6 +204,10 @@ def resolve_unet(ch, cin, cout, pol, train, B, H, W):
     if pol.head_fused and ch[0] == 32 and cout == 4 and st['conv9_2'].fwd.startswith('h2'):
         st['conv9_2'].fwd, st['conv9_2'].ks, st['conv10_1'].fwd = 'h2+head', 1, 'fused'
     if train:
+        for i in range(6, 10):             # the skip gradient of conv{i}_1 + MaxPool2d backward in one epilogue: needs the skip tensor's sign bits and codes
+            skip = st[f'conv{10 - i}_2']
+            st[f'conv{i}_1'].unpool = bool(pol.unpool_fused and (10 - i) in pol.unpool_levels and st[f'conv{i}_1'].dgrad == 'h2'
+                                           and skip.fwd in ('h2', 'h2+pool') and skip.codes)
         for i in range(1, 10):
             lvl = i - 1 if i <= 5 else 9 - i
             c = ch[lvl]

@@ -35,7 +35,7 @@ class _EngineBase:
 
     def _plan_for(self, B, H, W, train):
         """The per-layer plan of a forward on [B,.,H,W] (plan.py), cached per shape, mode and policy."""
-        key = (B, H, W, train, self._pol.key())
+        key = (B, H, W, train, self._pol.plan_key())
         if key not in self._plans:
             self._plans[key] = self._resolve(self._pol, train, B, H, W)
         return self._plans[key]
@@ -66,13 +66,17 @@ class _EngineBase:
         if policy is None:
             cur = dict(wino=self.policy.wino, wino_wgrad=self.policy.wino_wgrad, wino_mink=self.policy.wino_mink, x3=self.policy.x3,
                        thin=self.policy.thin, pool_fused=self.policy.pool_fused, h2=self.policy.h2)
-            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
+            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
                 if k in kw:
                     self._h2_sub[k] = bool(kw.pop(k))
+            if 'unpool_levels' in kw:                              # which encoder levels unpool_fused applies to (plan.py)
+                self._unpool_levels = tuple(sorted(int(l) for l in kw.pop('unpool_levels')))
             cur.update(kw)
             policy = ConvPolicy(**cur)                             # (defaults of the sub-switches: environment, as at construction)
             for k, v in self._h2_sub.items():
                 setattr(policy, k, v and policy.h2)
+            if getattr(self, '_unpool_levels', None) is not None:
+                policy.unpool_levels = self._unpool_levels
         self.policy = self._pol = policy
         self._pack_key = None        # re-pack for the other kernel family
         self._jobs_key = None
@@ -634,6 +638,7 @@ class UNetEngine(_EngineBase):
             wgrad('conv10_1', g_out8, self.cout, a['c9'], ch[0], taps=1)
             ops.conv_bwd_data(g_out8, self._wp['conv10_1'][1], g_cur, mask1=a['c9'], mode1=LRELU, taps=1)
             T.put(g_cur, 'head', fused=False)
+        skip_later = {}                    # encoder level -> (decoder layer, its output gradient): skip-gradient launches deferred to the pool's backward
         for i in range(9, 5, -1):          # decoder, top-down
             lvl = 9 - i
             wgrad(f'conv{i}_2', g_cur, ch[lvl], a[f'c{i}a'], ch[lvl])
@@ -643,7 +648,15 @@ class UNetEngine(_EngineBase):
             wgrad(f'conv{i}_1', g_a, ch[lvl], a[f'u{i}'], ch[lvl], x2=skip)
             g_u = gb(f'u{i}', a[f'u{i}'].shape)
             g_skip = gb(f'c{lvl + 1}', skip.shape)
-            dgrad(f'conv{i}_1', g_a, g_u, dx2=g_skip, mask2=skip, mode2=LRELU)
+            if plan[f'conv{i}_1'].unpool:
+                # only g_u is needed now: columns [0, c) of the pack (no mask: the plain forward epilogue).  The skip half -- columns [c, 2 c) -- is launched in
+                # the encoder loop, where the pooled map's gradient exists, and adds MaxPool2d's backward before it stores; g_a stays untouched until then
+                _, d, wslot = self._wp[f'conv{i}_1']
+                T.names[id(g_u)] = f'd1:conv{i}_1'
+                ops.conv_h2_bwd_data_unpool(g_a, T.of(g_a), d, wslot, 0, 2 * ch[lvl], g_u, amax_dx=T.slot(f'd1:conv{i}_1'))
+                skip_later[lvl + 1] = (f'conv{i}_1', g_a)
+            else:
+                dgrad(f'conv{i}_1', g_a, g_u, dx2=g_skip, mask2=skip, mode2=LRELU)
             below = a['c5'] if i == 6 else a[f'c{i - 1}']
             name = f'upv{i}'
             self._convt_wgrad(plan, name, F, T, below, g_u, G(name + '.weight', P[name + '.weight'].shape), G(name + '.bias', (ch[lvl],)), wsf, acc)
@@ -663,7 +676,14 @@ class UNetEngine(_EngineBase):
                 dgrad(f'conv{i}_1', g_a, g_p)
                 g_cur = gb(f'c{i - 1}', a[f'c{i - 1}'].shape)      # already holds the skip gradient
                 # (the skip gradient + the scattered pooled gradient: a new tensor, a new amax slot)
-                ops.maxpool_bwd(a[f'c{i - 1}'], g_p, g_cur, LRELU, 1, codes=a.get(f'pc{i - 1}'), amax_gx=T.slot(f'pool{i - 1}') if plan.h2 else None)
+                if (i - 1) in skip_later:
+                    # the deferred skip half of conv{11-i}_1's backward-data: act'(c{i-1}) x dgrad + unpool(g_p) stored once (csrc/conv_h2s.hip EK_BWDU)
+                    dname, g_dec = skip_later.pop(i - 1)
+                    _, d, wslot = self._wp[dname]
+                    ops.conv_h2_bwd_data_unpool(g_dec, T.of(g_dec), d, wslot, ch[lvl - 1], 2 * ch[lvl - 1], g_cur, bits=a[f'bits:conv{i - 1}_2'], mode=LRELU,
+                                                amax_dx=T.slot(f'pool{i - 1}'), gp=g_p, codes=a[f'pc{i - 1}'])
+                else:
+                    ops.maxpool_bwd(a[f'c{i - 1}'], g_p, g_cur, LRELU, 1, codes=a.get(f'pc{i - 1}'), amax_gx=T.slot(f'pool{i - 1}') if plan.h2 else None)
                 T.put(g_cur, f'pool{i - 1}', fused=True)
             else:
                 wgrad('conv1_1', g_a, ch[0], a['x8'], self.cin)

@@ -314,6 +314,30 @@ int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_
     return pnnp_igemm_h2s_launch(a, Cout, as_stream(stream));
 }
 
+// Columns [col0, col0 + C) of a backward-data pack with `cols` columns into ONE destination -- the pack is column-block-major (csrc/conv_h2s.hip: block nb of
+// 32 columns starts at nb x chunks x WBLK bytes), so a column range is the same kernel on an offset pack pointer.  With gp / codes: + the un-pooled gradient of
+// dx's pooled map in the epilogue (EK_BWDU), bit-identical to this launch without them followed by pnnp_maxpool2_bwd_codes_amax_f32(codes, gp, dx, .., mode, 1, ..).
+int pnnp_conv3x3_h2_bwd_data_unpool_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w, int col0, int cols,
+                                        float* dx, int C, const unsigned* bits, int mode, int accum, unsigned* amax_dx,
+                                        const float* gp, int gp_cs, const unsigned char* codes, int B, int H, int W, void* stream) {
+    if (!g || !w_h2_dgrad || !dx || B < 0 || H <= 0 || W <= 0 || Cout <= 0 || C <= 0 || col0 < 0 || cols <= 0) return PNNP_E_INVALID;
+    if ((col0 & 31) || (C & 31) || (cols & 31) || (int64_t)col0 + C > cols) return PNNP_E_INVALID;      // whole 32-column blocks inside the pack
+    if (B == 0) return PNNP_OK;
+    const int64_t blk_bytes = pnnp_h2_weight_bytes(Cout, 32);                                           // one 32-column block of this pack
+    H2Args a{};
+    bwd_args(a.g, g, Cout, static_cast<const char*>(w_h2_dgrad) + (col0 >> 5) * blk_bytes, dx, C, nullptr, 0, accum, nullptr, 0, nullptr, 0, 0, B, H, W);
+    if (bits) a.g.mask_mode[0] = mode;
+    a.amax_in[0] = amax_g; a.amax_w = amax_w; a.amax_out[0] = amax_dx;
+    a.bits_in[0] = bits; a.bits_nblk[0] = (C + 31) / 32;
+    a.dgrad_plain = !bits && !accum;
+    if (gp || codes) {
+        if (!gp || !codes) return PNNP_E_INVALID;
+        if (!bits || !mode) return PNNP_E_UNSUPPORTED;                                                  // (the launcher's rule, spelled out: mode survives only with bits)
+        a.unpool_g = gp; a.unpool_codes = codes; a.g.pool_cs = gp_cs;
+    }
+    return pnnp_igemm_h2s_launch(a, Cout, as_stream(stream));
+}
+
 int pnnp_conv3x3_h2_bwd_data_res_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                      float* dx, int C1, const float* addsrc, const float* mask, int mode, unsigned* amax_dx,
                                      int B, int H, int W, void* stream) {

@@ -81,6 +81,12 @@ __device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& 
 #ifndef H2S_PREBITS
 #define H2S_PREBITS 1                // backward-data with bit masks: the tile's mask words are requested in front of its last chunk (see prefetch_bits)
 #endif
+#ifndef H2S_PREPOOL
+#define H2S_PREPOOL 1                // EK_BWDU: the tile's pooled-gradient words and codes are requested in front of its last chunk too (0: at the start of the epilogue)
+#endif
+#ifndef H2S_COLS_BWDB
+#define H2S_COLS_BWDB 1              // an unmasked backward-data column range (H2Args::dgrad_plain) runs the EK_BWDB epilogue (0: EK_FWD; profiles/r7/ab_unpool_fused.txt)
+#endif
 #ifndef H2S_NSETS
 #define H2S_NSETS 2                  // producer register sets for the halo tile: 1 = a chunk's halo is requested at the END of the period before the one that splits it (round 5),
 #endif                               // 2 / 3 = at the START of that period / a period earlier still (profiles/r6/ab_producer_sets.txt)
@@ -91,7 +97,13 @@ __device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& 
 #endif
 // the epilogue a kernel carries (one straight-line path each): forward (no mask, no accumulation, no residual; writes sign bits when asked),
 // masked backward-data with float32 masks / with bit masks, the general one, forward + MaxPool2d(2)
-enum { EK_FWD = 0, EK_BWD = 1, EK_GEN = 2, EK_POOL = 3, EK_BWDB = 4, EK_HEAD = 5, EK_RES = 6 };
+enum { EK_FWD = 0, EK_BWD = 1, EK_GEN = 2, EK_POOL = 3, EK_BWDB = 4, EK_HEAD = 5, EK_RES = 6, EK_BWDU = 7 };
+// EK_BWDU (round 7): EK_BWDB for ONE destination that is the input of a MaxPool2d(2) as well as a skip connection (archs/Unet.py: conv1_2 .. conv4_2) -- the
+// bit-masked backward-data value + the un-pooled gradient of the pooled map, which csrc/misc.hip maxpool_bwd_codes_kernel used to add in a pass of its own
+// (a read-modify-write of the full-resolution map).  In the order of EK_RES: trade, add, track, store.  After the trade a lane's two stores are 4 consecutive
+// channels of one pixel each, so the pooled gradient is one 16-byte word and the codes one dword per store address, shared by the wave's two rows (a wave owns
+// rows 2 w, 2 w + 1: one window row).  Same float operations in the same order as the pass (t + ((k == argmax) ? g d : 0), the add ALSO when the term is
+// zero); the amax slot sees only what is stored (pixels outside the map are zeroed in front of the trade), as the pass's did: bit-identical, slot included.
 // EK_RES (round 6): a plain layer + a residual tensor of the destination's geometry, no activation, no mask (ResUnet: the second convolution of every
 // ResidualBlock, forward `conv + bias + shortcut` and backward-data `dgrad + g`, archs/modules.py:176-197) -- the general epilogue took 3.2 x the
 // forward epilogue's cycles for them (16-pixel x 64-byte stores, three loads per block: profiles/r6/gen_epilogue_stamps.txt).  Here: the residual
@@ -411,12 +423,15 @@ igemm_h2s_kernel(const H2Args ha) {
         put(E_POOLCS, a.pool_cs); put(E_CS0, a.dst_cs[0]); put(E_CS1, a.dst_cs[1]); put(E_MM0, a.mask_mode[0]); put(E_MM1, a.mask_mode[1]);
         put(E_AC0, a.accum[0]); put(E_AC1, a.accum[1]); put(E_DEXP, (unsigned)(-(se_x + se_w))); put(E_NBLK0, ha.bits_nblk[0]); put(E_NBLK1, ha.bits_nblk[1]);
         putp(E_DST0, a.dst[0]); putp(E_DST1, a.dst[1]); putp(E_MASK0, a.mask[0]); putp(E_MASK1, a.mask[1]); putp(E_ADD, a.addsrc);
-        putp(E_PDST, a.pool_dst); putp(E_PCODE, a.pool_codes); putp(E_BOUT, ha.bits_out); putp(E_BIN0, ha.bits_in[0]); putp(E_BIN1, ha.bits_in[1]);
+        if constexpr (EK == EK_BWDU) { putp(E_PDST, ha.unpool_g); putp(E_PCODE, ha.unpool_codes); }
+        else { putp(E_PDST, a.pool_dst); putp(E_PCODE, a.pool_codes); }
+        putp(E_BOUT, ha.bits_out); putp(E_BIN0, ha.bits_in[0]); putp(E_BIN1, ha.bits_in[1]);
         putp(E_HOUT, ha.head_out); putp(E_HRES, ha.head_res);
     }
     struct EpiArgs {
         int OH, OW, DH, DW, Ntot, n_split, act, pool_cs, cs0, cs1, mm0, mm1, ac0, ac1, dexp, nblk0, nblk1;
         float *dst0, *dst1, *pool_dst; const float *mask0, *mask1, *addsrc; unsigned char* pool_codes;
+        const float* unpool_g; const unsigned char* unpool_codes;      // (EK_BWDU) the pooled map's gradient and the forward pass's codes: inputs
         unsigned* bits_out; const unsigned *bin0, *bin1;
         float* head_out; const float* head_res;
         __device__ int dst_cs(int du) const { return du ? cs1 : cs0; }
@@ -435,7 +450,9 @@ igemm_h2s_kernel(const H2Args ha) {
         e.pool_cs = rl(E_POOLCS); e.cs0 = rl(E_CS0); e.cs1 = rl(E_CS1); e.mm0 = rl(E_MM0); e.mm1 = rl(E_MM1); e.ac0 = rl(E_AC0); e.ac1 = rl(E_AC1);
         e.dexp = rl(E_DEXP); e.nblk0 = rl(E_NBLK0); e.nblk1 = rl(E_NBLK1);
         e.dst0 = (float*)rp(E_DST0); e.dst1 = (float*)rp(E_DST1); e.mask0 = (const float*)rp(E_MASK0); e.mask1 = (const float*)rp(E_MASK1);
-        e.addsrc = (const float*)rp(E_ADD); e.pool_dst = (float*)rp(E_PDST); e.pool_codes = (unsigned char*)rp(E_PCODE);
+        e.addsrc = (const float*)rp(E_ADD);
+        if constexpr (EK == EK_BWDU) { e.unpool_g = (const float*)rp(E_PDST); e.unpool_codes = (const unsigned char*)rp(E_PCODE); e.pool_dst = nullptr; e.pool_codes = nullptr; }
+        else { e.pool_dst = (float*)rp(E_PDST); e.pool_codes = (unsigned char*)rp(E_PCODE); e.unpool_g = nullptr; e.unpool_codes = nullptr; }
         e.bits_out = (unsigned*)rp(E_BOUT); e.bin0 = (const unsigned*)rp(E_BIN0); e.bin1 = (const unsigned*)rp(E_BIN1);
         if constexpr (EK == EK_HEAD) { e.head_out = (float*)rp(E_HOUT); e.head_res = (const float*)rp(E_HRES); }
         return e;
@@ -445,7 +462,7 @@ igemm_h2s_kernel(const H2Args ha) {
 
     // (EK_BWDB) the tile's mask words, requested in FRONT of its last chunk (H2S_PREBITS, round 6): requested at the start of the epilogue, the first
     // mask_scale waited a memory latency for them with the matrix pipe idle -- per tile, ~2 000 cycles of a 13 000 ... 40 000-cycle tile on the shallow layers
-    unsigned mbits_pre[EK == EK_BWDB ? NT : 1];
+    unsigned mbits_pre[(EK == EK_BWDB || EK == EK_BWDU) ? NT : 1];
     auto prefetch_bits = [&](const Tile& tl) __attribute__((always_inline)) {
         const EpiArgs ea = epi_args();
         int lane_p = lane;
@@ -459,6 +476,37 @@ igemm_h2s_kernel(const H2Args ha) {
             const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(bp ? bp : ea.bin0), 0, a.B * tiles_y * tiles_x * nblk * NCW * 64 * 4, 0x00020000);
             const unsigned off = (unsigned)((((tile_id * nblk + (chw >> 5)) * NCW + wave) * 64 + lane_p) * 4);
             mbits_pre[k] = __builtin_amdgcn_raw_buffer_load_b32(rb, (ea.mask_mode(du) && bp && nwv < ea.Ntot) ? off : OOB, 0, 0);
+        }
+    };
+
+    // (EK_BWDU) the pooled gradient and the codes behind this lane's store addresses: [32-column block k][16-pixel half h][store instruction 1 / 2].  Instruction 1
+    // of (k, i, h) writes pixel (y0 + 2 w + i, x0 + (l & 7) + 16 h), channels 32 k + (l & 8 ? 16 : 0) + 4 (l >> 4) .. + 3, instruction 2 the pixel 8 on: pooled
+    // pixel ((y0 >> 1) + w, (x >> 1)) for both rows i -- the `po` of the EK_POOL forward epilogue, read.  Outside the map / the tensor: out of range, zeros.
+    constexpr int NPG = EK == EK_BWDU ? NT : 1;
+    f32x4 pg_pre[NPG][2][2]; unsigned pc_pre[NPG][2][2];
+    auto prefetch_pool = [&](const Tile& tl) __attribute__((always_inline)) {
+        const EpiArgs ea = epi_args();
+        int lane_p = lane;
+        asm volatile("" : "+v"(lane_p));
+        const int ph = ea.OH >> 1, pwd = ea.OW >> 1;
+        const int64_t pimg = (int64_t)tl.b * ph * pwd * ea.pool_cs;
+        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(ea.unpool_g + pimg), 0, ph * pwd * ea.pool_cs * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(ea.unpool_codes + pimg), 0, ph * pwd * ea.pool_cs, 0x00020000);
+        const int y = tl.y0 + wave * MT, xl = tl.x0 + (lane_p & 7);
+        const int chl = ((lane_p & 8) ? 16 : 0) + (lane_p >> 4) * 4;
+#pragma unroll
+        for (int k = 0; k < NPG; ++k) {
+            const int nwv = __builtin_amdgcn_readfirstlane(tl.n0 + k * 32);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const int x = xl + 16 * h + 8 * s2;
+                    const bool ok = nwv < ea.Ntot && y < ea.DH && x < ea.DW;
+                    const unsigned po = (unsigned)(((y >> 1) * pwd + (x >> 1)) * ea.pool_cs + nwv + chl);
+                    pg_pre[k][h][s2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, ok ? po * 4u : OOB, 0, 0));
+                    pc_pre[k][h][s2] = __builtin_amdgcn_raw_buffer_load_b32(rc, ok ? po : OOB, 0, 0);
+                }
         }
     };
 
@@ -701,9 +749,10 @@ igemm_h2s_kernel(const H2Args ha) {
         }
         // ---- FWD: no mask, no accumulation, no residual (every forward layer; sign bits on request);  BWD / BWDB: act' masks as float32
         // activations / as the forward kernel's bits (a destination without one requests them out of range: zeros come back, no memory traffic).
-        if constexpr (EK == EK_FWD || EK == EK_BWD || EK == EK_BWDB || EK == EK_HEAD || EK == EK_RES) {
-            constexpr bool RES = EK == EK_RES;
-            constexpr bool MASKED = EK == EK_BWD, BITS = EK == EK_BWDB, FWDL = EK == EK_FWD || EK == EK_HEAD;
+        if constexpr (EK == EK_FWD || EK == EK_BWD || EK == EK_BWDB || EK == EK_HEAD || EK == EK_RES || EK == EK_BWDU) {
+            constexpr bool RES = EK == EK_RES, UNP = EK == EK_BWDU;
+            constexpr bool MASKED = EK == EK_BWD, BITS = EK == EK_BWDB || UNP, FWDL = EK == EK_FWD || EK == EK_HEAD;
+            if constexpr (UNP && !H2S_PREPOOL) prefetch_pool(tl);
             f32x4 mk[(MASKED || RES) ? MB : 1][(MASKED || RES) ? NB : 1];      // [.][2 k] = what instruction 1 fetched, [.][2 k + 1] = instruction 2 (EK_RES: the residual words)
             unsigned mbits[NT];
             if constexpr (MASKED || RES) {
@@ -756,11 +805,12 @@ igemm_h2s_kernel(const H2Args ha) {
                                 o1 = take_bias(2 * i + h, 2 * k + 1, *reinterpret_cast<const f32x4*>(bias_lds + n0 + 32 * k + 16 + c4));
                             } else if constexpr (BITS) {
                                 const f32x4 v0 = take_raw(2 * i + h, 2 * k), v1 = take_raw(2 * i + h, 2 * k + 1);
-                                const float fneg = dsc * msl;
+                                // (EK_BWDU: a pixel outside the map becomes zero HERE, so that the amax slot sees exactly what is stored, as the pass's did)
+                                const float fpos = UNP ? (okp[i][h] ? dsc : 0.f) : dsc, fneg = UNP ? (okp[i][h] ? dsc * msl : 0.f) : dsc * msl;
 #pragma unroll
-                                for (int c = 0; c < 4; ++c) o0[c] = mask_scale(v0[c], mbits[k], dsc, fneg);
+                                for (int c = 0; c < 4; ++c) o0[c] = mask_scale(v0[c], mbits[k], fpos, fneg);
 #pragma unroll
-                                for (int c = 0; c < 4; ++c) o1[c] = mask_scale(v1[c], mbits[k], dsc, fneg);
+                                for (int c = 0; c < 4; ++c) o1[c] = mask_scale(v1[c], mbits[k], fpos, fneg);
                             } else {
                                 o0 = take(2 * i + h, 2 * k); o1 = take(2 * i + h, 2 * k + 1);
                             }
@@ -774,6 +824,26 @@ igemm_h2s_kernel(const H2Args ha) {
                             if constexpr (RES) {                       // trade first, then add what the two store instructions' addresses hold of the residual
                                 trade(o0, o1);
                                 o0 += mk[2 * i + h][2 * k]; o1 += mk[2 * i + h][2 * k + 1];
+                                track(o0); track(o1);
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rd, wo[k][i][h], 0, H2S_STORE_AUX);
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rd, wo2(k, i, h), 0, H2S_STORE_AUX);
+                                continue;
+                            }
+                            if constexpr (UNP) {
+                                // trade first, then add what the pooled map's gradient holds for the two store addresses: window position kp = 2 (y & 1) + (x & 1)
+                                // = 2 i + (lane & 1) (tiles start at even pixels), o = (kp == argmax) ? g x (element kp > 0 ? 1 : slope) : 0, v = t + o -- also when o is zero
+                                trade(o0, o1);
+                                const unsigned kp = 2u * i + (unsigned)(lane_e & 1);
+                                auto unpool = [&](f32x4& t, const f32x4 g4, const unsigned cw) __attribute__((always_inline)) {
+                                    const unsigned sg = cw >> kp;            // bit 8 c + 2: the sign of this pixel's window element of channel c
+#pragma unroll
+                                    for (int c = 0; c < 4; ++c) {
+                                        const float d = ((sg >> (8 * c + 2)) & 1u) ? 1.f : msl;
+                                        const float m = __fmul_rn(g4[c], d);
+                                        t[c] = __fadd_rn(t[c], (((cw >> (8 * c)) & 3u) == kp) ? m : 0.f);
+                                    }
+                                };
+                                unpool(o0, pg_pre[k][h][0], pc_pre[k][h][0]); unpool(o1, pg_pre[k][h][1], pc_pre[k][h][1]);
                                 track(o0); track(o1);
                                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rd, wo[k][i][h], 0, H2S_STORE_AUX);
                                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rd, wo2(k, i, h), 0, H2S_STORE_AUX);
@@ -890,7 +960,8 @@ igemm_h2s_kernel(const H2Args ha) {
 #ifdef H2S_STAMPS
         ++nch;
 #endif
-        if constexpr (EK == EK_BWDB && H2S_PREBITS) { if (g == nchunks - 1) prefetch_bits(cur); }
+        if constexpr ((EK == EK_BWDB || EK == EK_BWDU) && H2S_PREBITS) { if (g == nchunks - 1) prefetch_bits(cur); }
+        if constexpr (EK == EK_BWDU && H2S_PREPOOL) { if (g == nchunks - 1) prefetch_pool(cur); }
         mfma_chunk(st, img);
         H2S_T(t_mfma)
         // Experiment (H2S_TURNS, off): the two consumer waves of a SIMD (w, w + 4) TAKE TURNS with the epilogue of a tile -- waves 4-7 run it in
@@ -1066,6 +1137,15 @@ int pnnp_igemm_h2s_launch(const H2Args& ha, int chan_per_seg, hipStream_t s) {
         return launch_h2s<32, EK_HEAD>(b, s);
     }
     if (!a.dst[0]) return PNNP_E_INVALID;
+    if (ha.unpool_g || ha.unpool_codes) {
+        // bit-masked backward-data + the un-pooled gradient of the destination's pooled map (EK_BWDU): one destination, mask bits, nothing else; even sizes
+        if (!ha.unpool_g || !ha.unpool_codes || two || !a.mask_mode[0] || !ha.bits_in[0] || a.accum[0] || a.addsrc || a.bias || a.act || a.pool_dst || a.pool_codes ||
+            ha.bits_out || (a.OH & 1) || (a.OW & 1) || a.OH != a.DH || a.OW != a.DW || (a.pool_cs & 3) || a.pool_cs < a.Ntot || ((uintptr_t)ha.unpool_g & 15) ||
+            ((uintptr_t)ha.unpool_codes & 3))
+            return PNNP_E_UNSUPPORTED;
+        if ((int64_t)(a.OH / 2) * (a.OW / 2) * a.pool_cs * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+        return pnnp_h2_tile_columns(a.B, a.DH, a.DW, a.Ntot, 0) == 64 ? launch_h2s<64, EK_BWDU>(b, s) : launch_h2s<32, EK_BWDU>(b, s);
+    }
     if (a.pool_dst || a.pool_codes) {
         // fused MaxPool2d(2): plain forward layers only (one destination, no mask / residual / accumulate), even sizes
         if (!a.pool_dst || !a.pool_codes || two || a.mask_mode[0] || a.accum[0] || a.addsrc || (a.OH & 1) || (a.OW & 1) || a.OH != a.DH ||
@@ -1083,6 +1163,8 @@ int pnnp_igemm_h2s_launch(const H2Args& ha, int chan_per_seg, hipStream_t s) {
     if ((b0 || b1) && (!plain || a.act || a.bias)) return PNNP_E_UNSUPPORTED;  // bit masks: the masked backward-data epilogue only
     if (ha.bits_out && (m0 || m1 || !plain || two)) return PNNP_E_UNSUPPORTED; // sign bits: plain single-destination forward layers
     if (a.addsrc && !two && !a.accum[0] && !a.act && !m0 && !ha.bits_out) return wide ? launch_h2s<64, EK_RES>(b, s) : launch_h2s<32, EK_RES>(b, s);
+    if (H2S_COLS_BWDB && ha.dgrad_plain && plain && !two && !m0 && !a.bias && !a.act && !ha.bits_out && !ha.bits_in[0])
+        return wide ? launch_h2s<64, EK_BWDB>(b, s) : launch_h2s<32, EK_BWDB>(b, s);
     if (plain && !m0 && !m1) return wide ? launch_h2s<64, EK_FWD>(b, s) : launch_h2s<32, EK_FWD>(b, s);
     if (plain && !a.act && !a.bias) {
         if (b0 || b1) return wide ? launch_h2s<64, EK_BWDB>(b, s) : launch_h2s<32, EK_BWDB>(b, s);

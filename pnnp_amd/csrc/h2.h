@@ -42,6 +42,12 @@ struct H2Args {
     // split-K for small grids (csrc/conv_h2s.hip): ksplit > 1 workgroups share an output tile, each walking 1 / ksplit of the K chunks and writing raw partial
     // sums to image ks B + b of g.dst[0] = a [ksplit][B][OH][OW][cs] slab tensor (general epilogue, no bias / activation / mask / bits); 0 or 1: off
     int ksplit;
+    // backward-data into a tensor that was max-pooled as well (csrc/conv_h2s.hip EK_BWDU): the gradient of the pooled map [B][OH/2][OW/2][g.pool_cs] and the
+    // codes pnnp_maxpool2_fwd_codes_f32 / the pooled forward wrote; the epilogue adds the un-pooled term before the store.  Both null: an ordinary launch.
+    const float* unpool_g; const unsigned char* unpool_codes;
+    // a backward-data launch without any mask (a column range of a decoder layer: the gradient of the up-sampled half): take the bit-masked backward-data
+    // epilogue with no bits (every mask word requested out of range: the factor is 1) instead of the forward one -- the same values, no bias / sign-bit work
+    int dgrad_plain;
 };
 // Tile-private bit layout: the 16-row x 32-px x 32-channel block (image b, tile row ty, tile column tx, channel block cb) of a tensor with
 // nblk 32-channel blocks is 512 words; word 64 w + l belongs to lane l of consumer wave w, bit 31 - (((i 2 + h) 2 + jj) 4 + c) = element

@@ -34,7 +34,7 @@ class _Timed:
             PROFILE.append(self.rec)
 
 
-ABI_VERSION = 6                 # the PNNP_ABI_VERSION of include/pnnp_hip.h these wrappers (and the PackJob mirror below) were written against
+ABI_VERSION = 7                 # the PNNP_ABI_VERSION of include/pnnp_hip.h these wrappers (and the PackJob mirror below) were written against
 
 
 def _prep():
@@ -507,6 +507,20 @@ def conv_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx1, mask1=None, bits1=None,
         check(_prep().pnnp_conv3x3_h2_bwd_data_f32(ptr(g), Cout, ptr(amax_g), ptr(w_h2_dgrad), ptr(amax_w),
                                                    ptr(dx1), C1, ptr(mask1), ptr(bits1), mode1, accum1, ptr(amax_dx1),
                                                    ptr(dx2), C2, ptr(mask2), ptr(bits2), mode2, accum2, ptr(amax_dx2), B, H, W, stream()), 'conv_h2_bwd_data')
+
+
+def conv_h2_bwd_data_unpool(g, amax_g, w_h2_dgrad, amax_w, col0, cols, dx, bits=None, mode=0, accum=0, amax_dx=None, gp=None, codes=None):
+    """Columns [col0, col0 + C) of a backward-data pack with ``cols`` columns into ``dx`` [B,H,W,C] (the act' mask as sign bits, or none).  With ``gp`` / ``codes``
+    (the pooled map's gradient and the forward pass's codes) the kernel adds the un-pooled gradient before it stores: bit-identical to the plain launch
+    followed by ``maxpool_bwd(.., gp, dx, mode, 1, codes=codes, amax_gx=amax_dx)``, without that pass over the full-resolution map."""
+    require_cuda(g, w_h2_dgrad, dx, amax_g, amax_w, gp, codes)
+    B, H, W, Cout = g.shape
+    C1 = dx.shape[3]
+    nbytes = 4.0 * B * H * W * (C1 + Cout) + (1.25 * B * H * W * C1 if gp is not None else 0.0)      # (+ the pooled gradient and its one-byte codes)
+    with _Timed('conv9_dgrad_h2', 2.0 * B * H * W * Cout * C1 * 9, nbytes, sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, C1)):
+        check(_prep().pnnp_conv3x3_h2_bwd_data_unpool_f32(ptr(g), Cout, ptr(amax_g), ptr(w_h2_dgrad), ptr(amax_w), int(col0), int(cols), ptr(dx), C1, ptr(bits), mode,
+                                                          int(accum), ptr(amax_dx), ptr(gp), gp.shape[3] if gp is not None else 0, ptr(codes), B, H, W, stream()),
+              'conv_h2_bwd_data_unpool')
 
 
 def conv_h2_bwd_data_res(g, amax_g, w_h2_dgrad, amax_w, dx, addsrc, mask=None, mode=0, amax_dx=None):
