@@ -1058,15 +1058,9 @@ extern "C" int64_t pnnp_h2_bits_words(int B, int H, int W, int C) {
     return (int64_t)B * ((H + TH - 1) / TH) * ((W + 31) / 32) * ((C + 31) / 32) * NCW * 64;
 }
 
-// 64-column tiles unless the layer has fewer channels or they would leave CUs idle (csrc/conv_x3.hip); the pooled forward keeps 64 whenever it can
-extern "C" int pnnp_h2_tile_columns(int B, int H, int W, int N, int pool) {
-    if (N < 64) return 32;
-    if (pool) return 64;
-    int cus = pnnp_device_cus();
-    if (cus < 1) cus = 256;
-    const int64_t tiles64 = (int64_t)((W + 31) / 32) * ((H + TH - 1) / TH) * B * ((N + 63) / 64);
-    return tiles64 * 4 >= (int64_t)cus * 3 ? 64 : 32;
-}
+// tile width of a launch (the rule itself: pnnp_conv3_tile_columns, csrc/igemm.h -- shared with csrc/conv_x3.hip)
+static_assert(TH == 16, "pnnp_conv3_tile_columns counts 16-row tiles");
+extern "C" int pnnp_h2_tile_columns(int B, int H, int W, int N, int pool) { return pnnp_conv3_tile_columns(B, H, W, N, pool); }
 
 // split-K policy: how many K slices a [B][H][W] layer with `chunks` 16-channel chunks of K and N channels written should be cut into so that the grid fills
 // the chip (1 = no split): the smallest divisor of `chunks` that brings 32-column tiles x slices to 3/4 of the CUs, at least 2 chunks per slice

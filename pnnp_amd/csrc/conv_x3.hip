@@ -10,8 +10,6 @@
 int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);
 int pnnp_igemm_x3s_launch(const IgemmArgs& a, int wide, hipStream_t s);      // csrc/conv_x3s.hip
 
-namespace { constexpr int TH = 16; }                                          // rows of a tile (csrc/conv_x3s.hip)
-
 // a.w: the x3 pack of csrc/pack_jobs.hip (kind 2).  chan_per_seg: channels each K segment contributes (multiple of 8;
 // of 16 when there are several segments).  Only what the 3x3 / stride-1 layers need: in_mul = out_mul = 1, no sub-pixel N.
 int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s) {
@@ -40,13 +38,9 @@ int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s) {
             a.OW != a.DW || (a.pool_cs & 3) || a.pool_cs < a.Ntot || ((uintptr_t)a.pool_dst & 15) || ((uintptr_t)a.pool_codes & 3))
             return PNNP_E_UNSUPPORTED;
         if ((int64_t)(a.OH / 2) * (a.OW / 2) * a.pool_cs * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
-        return pnnp_igemm_x3s_launch(b, a.Ntot >= 64, s);
+        return pnnp_igemm_x3s_launch(b, pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 1) == 64, s);
     }
-    // 64-column tiles unless they leave CUs idle: a layer with fewer (16 x 32 px x 64 ch) tiles than CUs (conv5_1 backward-data at
-    // B = 16: 128; everything in a single-crop forward) runs on 32-column tiles, twice as many
-    int cus = pnnp_device_cus();
-    if (cus < 1) cus = 256;
-    const int64_t tiles64 = (int64_t)((a.DW + 31) / 32) * ((a.DH + TH - 1) / TH) * a.B * ((a.Ntot + 63) / 64);
-    const bool wide = a.Ntot >= 64 && tiles64 * 4 >= (int64_t)cus * 3;
+    // 64-column tiles unless they leave CUs idle: the fp16x2 family's rule (pnnp_conv3_tile_columns, csrc/igemm.h; exported as pnnp_h2_tile_columns)
+    const bool wide = pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 0) == 64;
     return pnnp_igemm_x3s_launch(b, wide, s);
 }

@@ -58,3 +58,16 @@ struct IgemmArgs {
     // (csrc/gemm_x3s.hip) max |stored value| per destination into an amax slot of the fp16x2 family (csrc/h2.h), or null
     unsigned* amax_out[2];
 };
+
+// GEMM columns per workgroup tile of the matrix-core 3x3 kernels (csrc/conv_h2s.hip, csrc/conv_x3s.hip: 16-row x 32-px pixel tiles, 32- and 64-column
+// instantiations).  64 unless the layer has fewer channels or the (16 x 32 px x 64 ch) tiles would leave CUs idle (conv5_1 backward-data at B = 16: 128;
+// everything in a single-crop forward): those run on 32-column tiles, twice as many.  The pooled forward keeps 64 whenever it can.  ONE rule for both
+// families: pnnp_h2_tile_columns exports it, the bf16x3 dispatch asks it too (tests/test_host_wide_cases.py).
+static inline int pnnp_conv3_tile_columns(int B, int H, int W, int N, int pool) {
+    if (N < 64) return 32;
+    if (pool) return 64;
+    int cus = pnnp_device_cus();
+    if (cus < 1) cus = 256;
+    const int64_t tiles64 = (int64_t)((W + 31) / 32) * ((H + 15) / 16) * B * ((N + 63) / 64);
+    return tiles64 * 4 >= (int64_t)cus * 3 ? 64 : 32;
+}
