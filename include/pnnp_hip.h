@@ -38,7 +38,7 @@ const char* pnnp_error_string(int code);
  * pnnp_pack_job_bytes() with its own sizeof(PnnpPackJob) before it passes a job table (pnnp_amd/ops.py does, on first use).
  *   6 (round 6): PnnpPackJob carries a trailing `amax` pointer since round 5 (an older caller's job ARRAY would be read with the wrong stride);
  *                pnnp_x3_supported refuses more than 1024 output channels (PNNP_E_UNSUPPORTED from the pnnp_conv3x3_x3_* entries beyond it). */
-#define PNNP_ABI_VERSION 7
+#define PNNP_ABI_VERSION 8
 int pnnp_abi_version(void);
 int pnnp_pack_job_bytes(void);
 /* Number of compute units etc. of the current device (0 on failure). */
@@ -632,6 +632,31 @@ typedef struct PnnpCensusJob {
 int pnnp_census_job_bytes(void);
 int64_t pnnp_census_table_words(int rows);
 int pnnp_range_census_f32(const PnnpCensusJob* jobs /*[device]*/, int njobs, uint64_t* table, long long step, void* stream);
+
+/* ---------------------------------------------------------------- score of a noise model (csrc/noise_score.hip)
+ * kl_div_norm with bl given (utils/kld_div.py:163-200): the integer-DN histogram KL divergence of two sample sets, with the reference's float
+ * edges (a key k = clip(rint(v (+ bl)), 0, wp) is counted in the bin np.histogram gives float32(k) / float32(wp) against
+ * np.arange(0, 1 + 1/wp, 1/wp): `lut`, int32 [wp + 1], -1 = in no bin; depends on wp alone, built on the host with numpy), its shift rule
+ * (p += bl, q += bl iff min(p) < 0 under numpy's NaN-propagating min) and n = every sample, NaNs included.  The caller's arrays are NOT
+ * modified (the reference adds bl in place).
+ *   pnnp_kl_div_norm_f32     p, q: [ncrops][n] float32 DN values, any element alignment.
+ *   pnnp_noise_score_f32     trainer_NF_SID.py:165-172: clean, real, sampled_noise [ncrops][n]; inputs = clip(clean, 0, 1), output = sampled_noise +
+ *                            inputs, p = rint((real - inputs) s), q = rint((output - inputs) s) in float32, s = float32(wp_data - bl_data); also the
+ *                            population std of real and of output (float64 shifted sums).  bl, wp are kl_div_norm's own (defaults 512, 16383).
+ * hist [ncrops][2][nbins] float64: y_p, y_q = counts / n.  result [ncrops][PNNP_NOISE_SCORE_ROW] float64: kl_fwd, kl_inv, kl_sym, gt_std, out_std,
+ * diff_p = 100 (gt_std - out_std) / gt_std (the three zero in DN mode), flags of p (1: some p < 0, 2: some NaN; the shift is on iff flags == 1), 0.
+ * ws: 16-byte aligned, pnnp_noise_score_ws_bytes(ncrops, n) bytes, need not be zeroed.  Behind one memset: pair mode one pass over the images
+ * (p, q are integers there: it counts a window index from which the key with and without the shift follows) + a finishing launch; DN mode a
+ * flags pass, a count pass and the finishing launch.  No synchronisation; 32-bit integer atomics and fixed-order float64 sums: bitwise
+ * reproducible.  PNNP_E_UNSUPPORTED before anything is launched: n >= 2^32, wp > PNNP_NOISE_SCORE_MAX_WP, nbins > wp_max + 1, and in pair
+ * mode a bl that is not an integer in [0, 512] (the window).  The bl=None branch of the reference (data-dependent edges) is not provided. */
+#define PNNP_NOISE_SCORE_MAX_WP 16383
+#define PNNP_NOISE_SCORE_ROW 8
+int64_t pnnp_noise_score_ws_bytes(int ncrops, int64_t n);
+int pnnp_kl_div_norm_f32(const float* p, const float* q, int ncrops, int64_t n, float bl, int wp, const int* lut, int nbins,
+                         void* ws, double* hist, double* result, void* stream);
+int pnnp_noise_score_f32(const float* clean, const float* real, const float* sampled_noise, int ncrops, int64_t n, float s, float bl, int wp,
+                         const int* lut, int nbins, void* ws, double* hist, double* result, void* stream);
 
 #ifdef __cplusplus
 }

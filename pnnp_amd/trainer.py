@@ -455,6 +455,7 @@ class NoiseFlowFitStep:
         B = hr.shape[0]
         plist = [process.sample_params_max(camera_type=self.camera_type, ratio=None, iso=iso if self.iso_table else None) for _ in range(B)]
         rows = process.pack_params(plist, hr.device)
+        self._pair_params = plist                # host copies (score: the camera's bl / wp)
         code = self.noise_code.lower()
         if 'g' in code and 'b' not in code and not self.tukey:
             raise NotImplementedError            # process.py:654
@@ -492,3 +493,26 @@ class NoiseFlowFitStep:
         self.optimizer.step()
         self.step_count += 1
         return nll.detach() + torch.log(ratio).mean(), sd_z * ratio.mean()
+
+    def score(self, hr, iso=1600, per_crop=False, return_tensors=False):
+        """The reference's per-epoch score of the proxy (trainer_NF_SID.py:163-173) on the clean crops ``hr`` [B,4,H,W] (CUDA): the
+        "real" pair drawn with ``make_pair`` at the step's counters, ``net.sample(clean=hr/ratio, iso=iso) * ratio`` under
+        ``no_grad``, then ``metrics.noise_model_score`` with the camera's bl / wp (device tensors, no synchronisation; crop 0 only
+        unless ``per_crop``; ``metrics.score_log_line`` formats the log text).  The module keeps the mode it is in -- the reference
+        scores in training mode, the caller decides -- and nothing is optimised.  ``return_tensors=True`` also returns
+        ``(hr_used, real, sampled_noise)``."""
+        from . import metrics
+        if not hr.is_cuda:
+            raise PnnpError('NoiseFlowFitStep needs CUDA tensors (no CPU path)')
+        training = self.net.training
+        real, ratio = self.make_pair(hr, iso)
+        if self.clip:
+            hr = hr.clamp(0, 1)                  # :442
+        try:
+            with torch.no_grad():
+                sampled = self.net.sample(clean=hr / ratio, iso=float(iso)) * ratio
+        finally:
+            self.net.train(training)
+        p0 = self._pair_params[0]
+        res = metrics.noise_model_score(hr, real, sampled, bl=p0['bl'], wp=p0['wp'], per_crop=per_crop)
+        return (res, (hr, real, sampled)) if return_tensors else res
