@@ -38,7 +38,7 @@ const char* pnnp_error_string(int code);
  * pnnp_pack_job_bytes() with its own sizeof(PnnpPackJob) before it passes a job table (pnnp_amd/ops.py does, on first use).
  *   6 (round 6): PnnpPackJob carries a trailing `amax` pointer since round 5 (an older caller's job ARRAY would be read with the wrong stride);
  *                pnnp_x3_supported refuses more than 1024 output channels (PNNP_E_UNSUPPORTED from the pnnp_conv3x3_x3_* entries beyond it). */
-#define PNNP_ABI_VERSION 8
+#define PNNP_ABI_VERSION 9
 int pnnp_abi_version(void);
 int pnnp_pack_job_bytes(void);
 /* Number of compute units etc. of the current device (0 on failure). */
@@ -657,6 +657,34 @@ int pnnp_kl_div_norm_f32(const float* p, const float* q, int ncrops, int64_t n, 
                          void* ws, double* hist, double* result, void* stream);
 int pnnp_noise_score_f32(const float* clean, const float* real, const float* sampled_noise, int ncrops, int64_t n, float s, float bl, int wp,
                          const int* lut, int nbins, void* ws, double* hist, double* result, void* stream);
+
+/* ---------------------------------------------------------------- differentiable distribution losses (csrc/ddl.hip)
+ * The linearly interpolated empirical CDF of a sample set at ascending points and the losses built on it, with the gradient with respect to
+ * the samples, in streaming passes: no sort.  Per point k: xc = clamp(x[k], min d, max d), c = #{d < xc}, hi = min{d >= xc}, lo = max{d < xc}
+ * (-inf if none), cdf[k] = ((float(c + 1) - (hi - xc) / (hi - lo)) - 1) / float(n - 1) in float32 in this order: bit for bit what
+ * CDFPPF.get_cdf computes on the CPU.  float32 only; 2 <= n < 2^31; 1 <= k <= PNNP_DDL_MAX_K (the KLD: k >= 2); anything else is
+ * PNNP_E_UNSUPPORTED before a launch.  PRECONDITION: x ascending (not checked).  NaN samples are not supported.  Among equal samples the LOWEST
+ * index is the bracket (and receives the gradient).  Arrays may start at any element.  No synchronisation, nothing allocated; integer
+ * atomics and fixed-order float64 sums only: bitwise reproducible.
+ *   pnnp_ddl_ws_bytes   the workspace of a call with nops (1 or 2) operands and k points; ws is 16-byte aligned and need not be zeroed.
+ *   pnnp_ecdf_f32       utils/kld_div.py:21-46 (CDFPPF: sort, inf padding, searchsorted, interpolation): cdf [k]; brackets [2k + 2] int32 =
+ *                       arg hi [k], arg lo [k] (-1: none), arg min, arg max -- the state the backward needs.
+ *   pnnp_ecdf_bwd_f32   the backward of :30-46 through sort / searchsorted / gather / clamp: grad [n] (zeroed here) of sum_k g[k] cdf[k]
+ *                       (g times scale[0] when scale, a device pointer, is given), evaluated term by term like ATen (0 where lo = -inf).
+ *   pnnp_cdf_loss_f32   :56-60 (CDFLoss): loss [1] = mean_k |cdf_output - cdf_gt|.
+ *   pnnp_kld_loss_f32   :62-78 (KLD, cdf2pdf): q, p = max(|cdf[k] - cdf[k+1]|, float32(1e-9)) of output, gt, both divided by the (detached)
+ *                       larger sum; loss [1] = sum p (log p - log q), float64 inside.
+ *                       Both: output [n_output], gt [n_gt]; cdf [2][k], brackets [2][2k + 2], dcdf [2][k] = dL/dcdf (output, gt): what
+ *                       pnnp_ecdf_bwd_f32 takes as g, with the upstream scalar as scale. */
+#define PNNP_DDL_MAX_K 4096
+int64_t pnnp_ddl_ws_bytes(int nops, int k);
+int pnnp_ecdf_f32(const float* data, int64_t n, const float* x, int k, void* ws, float* cdf, int* brackets, void* stream);
+int pnnp_ecdf_bwd_f32(const float* data, int64_t n, const float* x, int k, const int* brackets, const float* g, const float* scale /*[device], may be NULL*/,
+                      float* grad, void* stream);
+int pnnp_cdf_loss_f32(const float* output, int64_t n_output, const float* gt, int64_t n_gt, const float* x, int k, void* ws,
+                      float* cdf, int* brackets, float* loss, float* dcdf, void* stream);
+int pnnp_kld_loss_f32(const float* output, int64_t n_output, const float* gt, int64_t n_gt, const float* x, int k, void* ws,
+                      float* cdf, int* brackets, float* loss, float* dcdf, void* stream);
 
 #ifdef __cplusplus
 }

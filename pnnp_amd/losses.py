@@ -1,0 +1,218 @@
+"""Differentiable distribution losses on the device (reference: utils/kld_div.py:21-98; csrc/ddl.hip): the linearly interpolated
+empirical CDF of a sample set (``CDFPPF.get_cdf``), ``CDFLoss``, ``KLD``, ``cdf2pdf`` and the evaluation points ``get_x``, under the
+reference's names and signatures.  Everything but ``get_x`` takes float32 CUDA tensors and is a ``torch.autograd.Function``:
+``loss.backward()`` reaches whichever of ``output`` / ``gt`` requires grad.  The gradient stops at the samples and at the points
+``x`` (the reference would also differentiate with respect to ``x``; nothing in it does).
+
+Where the reference sorts every sample set, the kernels make two streaming passes (min / max, then a count, a minimum and a maximum
+per gap between points) and a K-element finish.  The cdf is the reference's CPU float32 value bit for bit.  Among equal samples the
+one with the LOWEST index brackets a point and receives its gradient (``torch.sort`` gives the upper neighbour's share to the
+highest index of a run of equal values; the sums per distinct value agree).  NaN samples are not supported.  The caller's tensors
+are never modified.  There is no CPU fallback: CPU tensors, another dtype or sizes outside 2 <= N < 2^31, 1 <= K <= MAX_K raise
+``PnnpError``.
+
+The kernels take ascending points.  ``assume_sorted=None`` (the default) checks that with one host read and, if ``x`` is not
+ascending, sorts it with ``torch.sort`` and un-permutes the result (K elements of plumbing); ``assume_sorted=True`` skips the check
+and the synchronisation it costs (``NoiseFlowFitStep.ddl`` does, its default points are ascending by construction)."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+MAX_K = 4096                     # PNNP_DDL_MAX_K
+
+
+def _ddl_lib():
+    L = _lib.lib()
+    if L.pnnp_ddl_ws_bytes.restype is not C.c_int64:
+        L.pnnp_ddl_ws_bytes.restype = C.c_int64
+    return L
+
+
+def _flat(t, what):
+    """The reference's ``.view(-1)`` of a sample set, as a contiguous detached float32 CUDA tensor (a copy only if it has to be)."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.PnnpError(f'{what}: expected a tensor, got {type(t).__name__}')
+    _lib.require_cuda(t)
+    if t.dtype != torch.float32:
+        raise _lib.PnnpError(f'{what}: the distribution losses take float32 tensors, got {t.dtype}')
+    n = t.numel()
+    if not 2 <= n < 2 ** 31:
+        raise _lib.PnnpError(f'{what}: {n} samples, the kernels take 2 <= N < 2^31')
+    return t.detach().reshape(-1).contiguous()
+
+
+def _points(x, min_k, what, assume_sorted):
+    """-> (ascending contiguous points, inverse permutation or None)"""
+    if not isinstance(x, torch.Tensor):
+        raise _lib.PnnpError(f'{what}: expected a tensor of points, got {type(x).__name__}')
+    _lib.require_cuda(x)
+    if x.dtype != torch.float32:
+        raise _lib.PnnpError(f'{what}: the points must be float32, got {x.dtype}')
+    k = x.numel()
+    if not min_k <= k <= MAX_K:
+        raise _lib.PnnpError(f'{what}: {k} points, the kernels take {min_k} <= K <= {MAX_K}')
+    x = x.detach().reshape(-1).contiguous()
+    if assume_sorted is None:
+        assume_sorted = k < 2 or bool((x[1:] >= x[:-1]).all())                   # the one host read
+    if assume_sorted:
+        return x, None
+    xs, perm = torch.sort(x)
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(k, device=x.device)
+    return xs.contiguous(), inv
+
+
+def _workspace(L, nops, k, device):
+    nbytes = int(L.pnnp_ddl_ws_bytes(nops, k))
+    if nbytes < 0:
+        _lib.check(nbytes, 'pnnp_ddl_ws_bytes')
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _backward(data, x, brackets, g, scale):
+    """grad [N] of sum_k g[k] cdf[k] (g times the device scalar ``scale`` if given) with respect to the flat samples"""
+    grad = torch.empty_like(data)
+    _lib.check(_ddl_lib().pnnp_ecdf_bwd_f32(_lib.ptr(data), C.c_int64(data.numel()), _lib.ptr(x), x.numel(), _lib.ptr(brackets), _lib.ptr(g),
+                                            _lib.ptr(scale), _lib.ptr(grad), _lib.stream()), 'pnnp_ecdf_bwd_f32')
+    return grad
+
+
+def ecdf_with_brackets(data, x):
+    """The cdf [K] of the flattened ``data`` at the ASCENDING points ``x`` and the kernel's bracket indices, int32 [2K + 2]: arg hi [K]
+    (the smallest sample >= the clamped point), arg lo [K] (the largest sample below it, -1 if none), arg min, arg max.  No autograd."""
+    flat = _flat(data, 'CDFPPF')
+    x, _ = _points(x, 1, 'CDFPPF', True)
+    L = _ddl_lib()
+    k = x.numel()
+    cdf = torch.empty(k, dtype=torch.float32, device=flat.device)
+    brackets = torch.empty(2 * k + 2, dtype=torch.int32, device=flat.device)
+    ws = _workspace(L, 1, k, flat.device)
+    _lib.check(L.pnnp_ecdf_f32(_lib.ptr(flat), C.c_int64(flat.numel()), _lib.ptr(x), k, _lib.ptr(ws), _lib.ptr(cdf), _lib.ptr(brackets),
+                               _lib.stream()), 'pnnp_ecdf_f32')
+    return cdf, brackets
+
+
+class _ECDF(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, x):
+        flat = _flat(data, 'CDFPPF')
+        cdf, brackets = ecdf_with_brackets(flat, x)
+        ctx.save_for_backward(flat, x, brackets)
+        ctx.shape = data.shape
+        return cdf
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        flat, x, brackets = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        return _backward(flat, x, brackets, g, None).view(ctx.shape), None
+
+
+class _Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, gt, x, kind):
+        entry = {'cdf': 'pnnp_cdf_loss_f32', 'kld': 'pnnp_kld_loss_f32'}[kind]
+        o, g = _flat(output, kind + ' loss: output'), _flat(gt, kind + ' loss: gt')
+        if o.device != g.device or x.device != o.device:
+            raise _lib.PnnpError(f'{kind} loss: output, gt and the points are on different devices')
+        L = _ddl_lib()
+        k = x.numel()
+        dev = o.device
+        cdf = torch.empty(2, k, dtype=torch.float32, device=dev)
+        dcdf = torch.empty(2, k, dtype=torch.float32, device=dev)
+        brackets = torch.empty(2, 2 * k + 2, dtype=torch.int32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _workspace(L, 2, k, dev)
+        _lib.check(getattr(L, entry)(_lib.ptr(o), C.c_int64(o.numel()), _lib.ptr(g), C.c_int64(g.numel()), _lib.ptr(x), k, _lib.ptr(ws),
+                                     _lib.ptr(cdf), _lib.ptr(brackets), _lib.ptr(loss), _lib.ptr(dcdf), _lib.stream()), entry)
+        ctx.save_for_backward(o, g, x, brackets, dcdf)
+        ctx.shapes = (output.shape, gt.shape)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gup):
+        o, g, x, brackets, dcdf = ctx.saved_tensors
+        scale = gup.to(torch.float32).reshape(1).contiguous()
+        grads = [None, None]
+        for i, data in enumerate((o, g)):
+            if ctx.needs_input_grad[i]:
+                grads[i] = _backward(data, x, brackets[i], dcdf[i], scale).view(ctx.shapes[i])
+        return grads[0], grads[1], None, None
+
+
+class CDFPPF(torch.nn.Module):
+    """utils/kld_div.py:21-46: the empirical CDF of ``data`` (1-D in the reference; any shape is flattened), linearly interpolated
+    between order statistics.  Nothing is sorted or stored: ``get_cdf`` reads ``data`` when it is called."""
+
+    def __init__(self, data, inf=None):
+        super().__init__()
+        if inf is not None:
+            raise _lib.PnnpError('CDFPPF(inf=...): only the default padding (inf) is provided')
+        _flat(data, 'CDFPPF')
+        self.data = data
+
+    def get_cdf(self, x, assume_sorted=None):
+        xs, inv = _points(x, 1, 'CDFPPF.get_cdf', assume_sorted)
+        if xs.device != self.data.device:
+            raise _lib.PnnpError('CDFPPF.get_cdf: the points and the samples are on different devices')
+        cdf = _ECDF.apply(self.data, xs)
+        if inv is not None:
+            cdf = cdf[inv]
+        return cdf.view(x.shape)
+
+    def forward(self, x):
+        return self.get_cdf(x)
+
+
+def cdf2pdf(data):
+    """utils/kld_div.py:76-78: |data[k] - data[k+1]| (the reference's conv1d with the kernel [1, -1]); K elements, plain tensor ops."""
+    _lib.require_cuda(data)
+    d = data.reshape(-1)
+    return torch.abs(d[:-1] - d[1:])
+
+
+def CDFLoss(output, gt, x_cdf, assume_sorted=None):
+    """utils/kld_div.py:56-60: mean_k |cdf_output(x_k) - cdf_gt(x_k)|, a 0-dim device tensor.  The mean does not depend on the order
+    of the points, so points that are not ascending are simply sorted."""
+    xs, _ = _points(x_cdf, 1, 'CDFLoss', assume_sorted)
+    return _Loss.apply(output, gt, xs, 'cdf')
+
+
+def KLD(output, gt, x_pdf, assume_sorted=None):
+    """utils/kld_div.py:62-74: KL divergence of the two difference quotients of the interpolated CDFs (q from ``output``, p from ``gt``,
+    clamped at 1e-9, divided by the detached larger sum), a 0-dim device tensor.  The differences depend on the order of the points:
+    for points that are not ascending the loss is composed from ``get_cdf`` and K-element tensor ops in the given order."""
+    xs, inv = _points(x_pdf, 2, 'KLD', assume_sorted)
+    if inv is None:
+        return _Loss.apply(output, gt, xs, 'kld')
+    _flat(gt, 'kld loss: gt')
+    q = cdf2pdf(_ECDF.apply(output, xs)[inv]).clamp_min(1e-9)
+    p = cdf2pdf(_ECDF.apply(gt, xs)[inv]).clamp_min(1e-9)
+    factor = torch.max(q.sum(), p.sum()).detach()
+    q, p = q / factor, p / factor
+    return torch.sum(p * (torch.log(p) - torch.log(q)))
+
+
+def get_x(sigma=4, size=1000, mode='uniform', random=True):
+    """utils/kld_div.py:80-98: evaluation points in (0, 1) -- 'uniform': evenly spaced; 'cdf': the normal CDF of evenly spaced points
+    over [-sigma, sigma], jittered by N(0, 10^-sigma) and clipped to [0, 1]; 'icdf': normal quantiles of evenly spaced probabilities
+    jittered by N(0, (10^-sigma / 2)^2).  Host code on torch's global RNG: the same draws as the reference under ``torch.manual_seed``.
+    Returns a CPU float32 tensor (ascending, except that the reference returns any other ``mode`` sorted too)."""
+    tiny = 10 ** (-sigma)
+    x = torch.linspace(tiny, 1 - tiny, size)
+    if mode == 'uniform':
+        return x
+    normal = torch.distributions.Normal(loc=0, scale=1)
+    if mode == 'cdf':
+        x = normal.cdf(x * sigma * 2 - sigma)
+        if random:
+            x = torch.clamp(x + torch.randn(size) / 10 ** sigma, 0, 1)
+    elif mode == 'icdf':
+        if random:
+            x = x + (torch.randn(size) / 2) / 10 ** sigma
+        x = normal.icdf(x.clamp(tiny, 1 - tiny))
+    return torch.sort(x)[0]

@@ -34,7 +34,7 @@ class _Timed:
             PROFILE.append(self.rec)
 
 
-ABI_VERSION = 8                 # the PNNP_ABI_VERSION of include/pnnp_hip.h these wrappers (and the PackJob mirror below) were written against
+ABI_VERSION = 9                 # the PNNP_ABI_VERSION of include/pnnp_hip.h these wrappers (and the PackJob mirror below) were written against
 
 
 def _prep():

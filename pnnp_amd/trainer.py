@@ -516,3 +516,33 @@ class NoiseFlowFitStep:
         p0 = self._pair_params[0]
         res = metrics.noise_model_score(hr, real, sampled, bl=p0['bl'], wp=p0['wp'], per_crop=per_crop)
         return (res, (hr, real, sampled)) if return_tensors else res
+
+    def ddl(self, hr, iso=1600, kind='cdf', x=None):
+        """A differentiable distribution loss (``losses.CDFLoss`` for ``kind='cdf'``, ``losses.KLD`` for ``'kld'``; utils/kld_div.py:56-74)
+        between the proxy's samples and the real noise of the pair that ``score`` draws: ``make_pair`` at the step's counters and
+        ``net.sample(clean=hr/ratio, iso=iso) * ratio`` under ``no_grad``, compared with ``real - hr``.  Returns a 0-dim device tensor
+        without synchronising.  ``x``: ascending float32 CUDA points; by default ``losses.get_x(size=1000, mode='uniform')`` mapped
+        affinely onto the real noise's [min, max] with device ops.  The module keeps its mode; nothing is optimised (a backward through
+        ``NoiseFlow.sample`` is not provided: the gradient with respect to the samples is where ``losses`` stops)."""
+        from . import losses
+        if kind not in ('cdf', 'kld'):
+            raise PnnpError(f"NoiseFlowFitStep.ddl: kind = {kind!r}, expected 'cdf' or 'kld'")
+        if not hr.is_cuda:
+            raise PnnpError('NoiseFlowFitStep needs CUDA tensors (no CPU path)')
+        training = self.net.training
+        real, ratio = self.make_pair(hr, iso)
+        if self.clip:
+            hr = hr.clamp(0, 1)                  # :442
+        try:
+            with torch.no_grad():
+                sampled = self.net.sample(clean=hr / ratio, iso=float(iso)) * ratio
+        finally:
+            self.net.train(training)
+        noise = real - hr
+        if x is None:
+            lo, hi = noise.min(), noise.max()
+            x = lo + losses.get_x(size=1000, mode='uniform').to(hr.device) * (hi - lo)
+            sorted_ = True                       # ascending by construction: no host read
+        else:
+            sorted_ = None
+        return (losses.CDFLoss if kind == 'cdf' else losses.KLD)(sampled, noise, x, assume_sorted=sorted_)
