@@ -421,7 +421,15 @@ int pnnp_conv3x3s2_bwd_weight_f32(const float* g, int Cout, const float* x, int 
                                   float* dbias /*or null*/, int B, int H, int W, int accumulate,
                                   float* workspace, int64_t workspace_floats, void* stream);
 /* MaxPool2d(2) (archs/Unet.py:57-69); backward routes to the first maximum of each window,
- * multiplies by act'(x) and optionally accumulates into gx (skip-connection gradient). */
+ * multiplies by act'(x) and optionally accumulates into gx (skip-connection gradient).
+ * Semantics of a window (a, b, c, d) = positions (0,0) (0,1) (1,0) (1,1), shared bit for bit by all four implementations -- pnnp_maxpool2_fwd_f32,
+ * pnnp_maxpool2_fwd_codes_f32 and the epilogues of pnnp_conv3x3_x3_fwd_pool_f32 / pnnp_conv3x3_h2_fwd_pool_f32 (tests/test_gpu_misc.py):
+ *   value   fmaxf(fmaxf(a, b), fmaxf(c, d)).  On finite data and infinities this is F.max_pool2d.  A NaN beside a number is DROPPED (fmaxf returns
+ *           the other operand): the pooled value is NaN only if all four elements are, where F.max_pool2d returns NaN for any.  (The skip connection
+ *           carries the same NaN to the loss, which does propagate it.)  Of +0.0 and -0.0 either may be returned.
+ *   argmax  a scan from position 0 that moves to position k only on x[k] > x[arg]: the FIRST maximum wins a tie (+0.0 and -0.0 tie), and a comparison
+ *           against a NaN is false, so a NaN at position 0 keeps the argmax and a later NaN never takes it.
+ *   sign    x > 0: 0 for +0.0, -0.0 and NaN. */
 int pnnp_maxpool2_fwd_f32(const float* x, float* y, int B, int H, int W, int C, void* stream);
 int pnnp_maxpool2_bwd_f32(const float* x, const float* gy, float* gx, int B, int H, int W, int C,
                           int act_mode, int accumulate, void* stream);
