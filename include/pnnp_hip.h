@@ -298,7 +298,7 @@ int pnnp_conv3x3s2_h2_fwd_f32(const float* x, int Cin, const unsigned* amax_x, c
                               unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
 int pnnp_conv3x3s2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_s2dgrad, const unsigned* amax_w, float* dx, int Cin,
                                    const float* mask /*or null*/, int mode, int accum, unsigned* amax_dx /*or null*/, int B, int H, int W, void* stream);
-/* ... and their backward-weights (csrc/wgrad_h2g.hip): contracts of the _x3_ entries + the amax slots of the two tensors that are split; shapes and
+/* ... and their backward-weights (csrc/wgrad_h2g.hip: the kernel of csrc/wgrad_g.h on this scheme): contracts of the _x3_ entries + the amax slots of the two tensors that are split; shapes and
  * workspace: pnnp_h2g_wgrad_supported / _workspace_floats (kind as pnnp_x3g_wgrad_supported: everything it takes, and stride-2 with Cout % 64 == 0) */
 int pnnp_h2g_wgrad_supported(int kind, int M, int N);
 int64_t pnnp_h2g_wgrad_workspace_floats(int kind, int B, int UH, int UW, int M, int N);
@@ -361,7 +361,7 @@ int pnnp_conv3x3_x3_bwd_weight_f32(const float* g, int g_cs, int Cout, const flo
                                    const float* x2 /*or null*/, int x2_cs, int C2, float* dW, float* dbias /*or null*/,
                                    int B, int H, int W, int accumulate, float* workspace, int64_t workspace_floats, void* stream);
 
-/* backward-weight of the POINTWISE / STRIDED layers on the same scheme (csrc/wgrad_x3g.hip, round 4; they ran on the fp32 matrix cores
+/* backward-weight of the POINTWISE / STRIDED layers on the same scheme (csrc/wgrad_x3g.hip; geometries, tiles, staging layout: csrc/wgrad_g.h; round 4; they ran on the fp32 matrix cores
  * before): kind 0 = Conv2d 1x1 (M = Cout, N = C1 + C2; replaces pnnp_conv_bwd_weight_f32 with taps = 1, archs/modules.py:184-187),
  * 1 = ConvTranspose2d 2x2 stride 2 (M = Cin, N = Cout; replaces pnnp_convt2x2_bwd_weight_f32, archs/Unet.py:35-47),
  * 2 = Conv2d 3x3 stride 2 (M = Cout, N = Cin; replaces pnnp_conv3x3s2_bwd_weight_f32, archs/ResUnet.py:18-27).  Same contracts as

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/pnnp_hip.h"
 
 #define PNNP_WAVE 64
@@ -57,6 +58,12 @@ static inline int pnnp_persistent_grid(int64_t tiles) {
     if (cus < 1) cus = 256;
     const int64_t wgs = (int64_t)cus * pnnp_get_persistent_split();
     return (int)(wgs < tiles ? wgs : tiles);
+}
+
+// compile-time loop: f(std::integral_constant<int, I>) for I in [I, N)
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
 
 // amax slots of the fp16x2 family (csrc/h2.h): a wave's largest |stored value| -> atomicMax on the slot (non-negative floats order like their

@@ -16,7 +16,6 @@
 //   * forward: writes the SIGN BITS of the activated output, 32 per lane, in a tile-private layout; backward-data reads them back as the
 //     LeakyReLU' / ReLU' mask -- 4 bytes per lane and 32-channel block where the float32 activation cost 8 x 16.
 #include "h2.h"
-#include <type_traits>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -49,24 +48,9 @@ template <int BN> struct SCfg {
     static_assert(LDS_BYTES <= 160 * 1024, "a workgroup's LDS");
 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
 __device__ __forceinline__ int xcd_remap(int id, int n) {
     const int q = n >> 3, r = n & 7, x = id & 7, k = id >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-// hi = f16(a s), lo = f16(a s - hi) of two values, packed (low half = a0): v_fma_mix*_f16 computes the fma in float32 and rounds ONCE to fp16
-// (nearest even); a s is exact (power of two), a s - hi is exact in float32 (the residual of a 24-bit significand after its top 11 bits), so
-// both pieces are correctly rounded (tools/ubench/h2_probe.hip: 65536 values bit for bit against the host)
-__device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& hi, unsigned& lo) {
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(a0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(a1), "v"(s), "v"(h));
-    hi = h; lo = l;
 }
 
 #ifndef H2S_STORE_AUX

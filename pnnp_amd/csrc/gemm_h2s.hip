@@ -17,7 +17,6 @@
 // Tiles: 256 px x 128 columns (4 x 2 consumer waves of 64 px x 64), 256 px x 64 (4 x 2 waves of 64 px x 32) and, for GEMMs with 32 (mod 64) columns, 256 px x 32
 // (4 x 1 waves of 64 px x 32; the other four consumer waves only keep the barriers -- these layers move 32 KB per item for 384 matrix-pipe cycles: HBM-bound).
 #include "h2.h"
-#include <type_traits>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -54,22 +53,9 @@ template <int BN, int WN_> struct GCfg {
     static_assert(A * 2 * NSL + (A - 1) * DPW <= 63, "the producers' vmcnt");
 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
 __device__ __forceinline__ int xcd_remap(int id, int n) {
     const int q = n >> 3, r = n & 7, x = id & 7, k = id >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-// hi = f16(a s), lo = f16(a s - hi) of two values, packed (low half = a0): csrc/conv_h2s.hip split_h2
-__device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& hi, unsigned& lo) {
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(a0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(a1), "v"(s), "v"(h));
-    hi = h; lo = l;
 }
 
 #ifdef GHS_STAMPS                 // debug build: cycle sums per wave, dumped into dst[0] (tools/gx_stamps.py --spec)

@@ -15,7 +15,7 @@
 // One s_barrier per item.  Tiles: 256 px x 128 columns (4 x 2 consumer waves of 64 px x 64), 512 px x 64 (8 x 1), 256 px x 64 (4 x 2 waves
 // of 64 px x 32: small layers), 512 px x 32.
 #include "igemm.h"
-#include <type_traits>
+#include "x3.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -51,23 +51,9 @@ template <int BN, int WN_> struct GCfg {
     static_assert(A * 2 * NSL + (A - 1) * DPW <= 63, "the producers' vmcnt");
 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
 __device__ __forceinline__ int xcd_remap(int id, int n) {
     const int q = n >> 3, r = n & 7, x = id & 7, k = id >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {      // RNE, low half = a
-    unsigned r; asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ void split2(float a0, float a1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(a0, a1);
-    const float r0 = a0 - __uint_as_float(h << 16), r1 = a1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
 }
 
 

@@ -55,3 +55,28 @@ struct H2Args {
 // so a lane reads back exactly the word the same lane position wrote: 4 bytes per lane instead of 8 x 16.
 int pnnp_igemm_h2s_launch(const H2Args& a, int chan_per_seg, hipStream_t s);
 int pnnp_h2_splitk_reduce_launch(const float* slab, int S, const float* bias, float* y, unsigned* bits, unsigned* amax, int B, int H, int W, int N, int act, hipStream_t st);
+
+// hi = f16(a s), lo = f16(a s - hi) of two values, packed (low half = a0): v_fma_mix*_f16 computes the fma in float32 and rounds ONCE to fp16
+// (nearest even); a s is exact (power of two), a s - hi is exact in float32 (the residual of a 24-bit significand after its top 11 bits), so
+// both pieces are correctly rounded (tools/ubench/h2_probe.hip: 65536 values bit for bit against the host)
+__device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& hi, unsigned& lo) {
+    unsigned h, l;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(s));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(s));
+    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(a0), "v"(s), "v"(h));
+    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(a1), "v"(s), "v"(h));
+    hi = h; lo = l;
+}
+// ... as two steps, for a kernel that deals them over its MFMA gaps (csrc/wgrad_g.h)
+__device__ __forceinline__ unsigned h2_hi(float a0, float a1, float s) {
+    unsigned h;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(s));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(s));
+    return h;
+}
+__device__ __forceinline__ unsigned h2_lo(float a0, float a1, float s, unsigned h) {
+    unsigned l;
+    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(a0), "v"(s), "v"(h));
+    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(a1), "v"(s), "v"(h));
+    return l;
+}

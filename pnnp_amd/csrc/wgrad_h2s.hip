@@ -5,9 +5,7 @@
 // on the fly: G with 2^se_g (odd pixel splits: -2^se_g, the alternating sign costs nothing), X with 2^se_x from the amax slots of the
 // tensors; the slab values are multiplied by 2^-(se_g + se_x) where they leave the accumulators.  The LDS images are two planes instead of
 // three, so pixel tiles could be taller; only the 32 x 64 tile's (3 rows instead of 2) fit the producers' registers without spilling.
-#include "common.h"
 #include "h2.h"
-#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -48,11 +46,6 @@ constexpr unsigned OOB = 0x80000000u;
 #define WX3_ALT_SIGN 1                 // odd pixel splits accumulate -G * X (csrc/wgrad_x3.hip: the matrix core's accumulation rounds toward minus infinity)
 #endif
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
-
 template <int MO, int NO, int TH, int MW = 1> struct WsCfg {
     // MW: 32 x 32 blocks along M that ONE consumer owns (1, or 2 = both of a 64-row tile: the X words of a tap then feed two blocks, 20 transposed
     // reads per 18 MFMAs instead of 16 per 9 -- this kernel is LDS-bandwidth-bound with one block per wave: 12 waves x 16 reads x 512 B per k-step
@@ -67,16 +60,6 @@ template <int MO, int NO, int TH, int MW = 1> struct WsCfg {
     static_assert((GPIX * 8) % GT == 0, "G slots divide evenly (the bias sums count every pixel once)");
     static_assert(LDS_BYTES <= 160 * 1024 && LDS_BYTES >= NCW * 16 * 64 * 4, "LDS budget (images; the final reduction aliases them, one accumulator block at a time)");
 };
-
-// hi = f16(a s), lo = f16(a s - hi) of two values, packed (csrc/conv_h2s.hip)
-__device__ __forceinline__ void split_h2(float a0, float a1, float s, unsigned& hi, unsigned& lo) {
-    unsigned h, l;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(a1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(a0), "v"(s), "v"(h));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(a1), "v"(s), "v"(h));
-    hi = h; lo = l;
-}
 
 template <int MO, int NO, int TH, int MW>
 __global__ void __launch_bounds__(NTHR, 1)

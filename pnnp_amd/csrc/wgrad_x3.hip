@@ -94,7 +94,7 @@ int wx3_splits(int B, int H, int W, int M, int N, int share) {
 }  // namespace
 
 // slabs [Z][taps][M][N] (+ bias slabs [Z][nb] behind them) -> dW in the parameter's layout [M][N][taps] (+ dbias), alternating signs over z
-// (also used by csrc/wgrad_x3g.hip)
+// (also used by csrc/wgrad_g.h)
 int pnnp_wx3_reduce_launch(const float* slab, float* dW, int64_t mn, int taps, int Z, int accumulate,
                            const float* bias_slab, float* dbias, int nb, hipStream_t st) {
     const int64_t n = mn * taps, ntot = n + (bias_slab ? nb : 0);       // n % 32 == 0 (channels in multiples of 32)

@@ -11,8 +11,7 @@
 //     ahead) -> hi / mid / lo split -> the other LDS image; the bias gradient (column sums of G) on the way.
 // 1024 threads, <= 128 registers each, one barrier per pixel tile.  (The 16 x 16 x 32 MFMA shape was tried in this kernel too -- commit 936596b,
 // WXS_M16: parity-green, 44 transposed reads per k-step instead of 24, 4-5 % slower; profiles/r4/ab_wgrad_specialised.txt.)
-#include "common.h"
-#include <type_traits>
+#include "x3.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -53,17 +52,6 @@ template <int MO, int NO, int TH> struct WsCfg {
     static_assert((GPIX * 8) % GT == 0, "G slots divide evenly (the bias sums count every pixel once)");
     static_assert(LDS_BYTES <= 160 * 1024 && LDS_BYTES >= NCW * 16 * 64 * 4, "LDS budget (images; the final reduction aliases them)");
 };
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {      // RNE, low half = a
-    unsigned r; asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ void split2(float a0, float a1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(a0, a1);
-    const float r0 = a0 - __uint_as_float(h << 16), r1 = a1 - __uint_as_float(h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
 
 template <int MO, int NO, int TH>
 __global__ void __launch_bounds__(NTHR, 1)

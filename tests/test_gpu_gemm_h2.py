@@ -252,3 +252,59 @@ def test_convt_h2_bwd_weight_tiles_per_workgroup(B):
     err = (dW.double() - ref).norm() / ref.norm()
     assert err < 2e-6, (B, float(err))
     assert (db.double() - g.double().sum((0, 1, 2))).abs().max() < 1e-5 * g.double().abs().sum((0, 1, 2)).max()
+
+
+# The six tile configurations that bf16x3 and fp16x2 share (csrc/wgrad_g.h), each at a map that is ragged in the tile's width (and in its rows where a tile
+# has two) and has between one and two pixel tiles per workgroup on 256 compute units: some workgroups then run out of tiles one round before the others
+# (the refill order and the no-next-tile path).  (kind, M, N, B, UH, UW) with pixel tiles / workgroups per output tile:
+_SHARED_WGRAD_TILES = [
+    ('convT 256 x 64', 'CT', 256, 64, 3, 24, 72),      # 16 x 1 px: 5 * 24 * 3 = 360 / 256
+    ('convT 128 x 64', 'CT', 128, 64, 3, 24, 72),      # 16 x 1 px: 360 / 256
+    ('convT 64 x 32', 'CT', 64, 64, 4, 25, 72),        # 32 x 2 px: 3 * 13 * 4 = 156 / 128
+    ('s2 128 x 32', 'S2', 128, 64, 3, 25, 40),         # 32 x 1 px: 2 * 25 * 3 = 150 / 128
+    ('1x1 128 x 128', 'PW', 128, 128, 3, 50, 40),      # 32 x 1 px: 2 * 50 * 3 = 300 / 256
+    ('1x1 64 x 128', 'PW', 64, 128, 3, 50, 40),        # 32 x 1 px: 300 / 256
+]
+
+
+def test_pointwise_weight_gradients_bf16x3_and_h2_share_their_bias_sums():
+    """Both schemes run ONE kernel text (csrc/wgrad_g.h): the bias gradient is summed from the unscaled float32 values in the same fixed order over the same
+    pixel split, so the two entries return it BIT-EQUAL; dW of each stays at the float64 bar of _wgrad_check."""
+    from pnnp_amd import _lib, ops
+    if _lib.lib().pnnp_device_cus() != 256:
+        pytest.skip('the shapes below give one to two pixel tiles per workgroup on 256 compute units')
+    gen = torch.Generator(device='cuda').manual_seed(33)
+    rnd = lambda *s: torch.randn(*s, device='cuda', generator=gen)
+    for name, kind, M, N, B, UH, UW in _SHARED_WGRAD_TILES:
+        k = dict(CT=ops.X3G_CT, S2=ops.X3G_S2, PW=ops.X3G_PW)[kind]
+        assert ops.x3g_wgrad_supported(k, M, N) and ops.h2g_wgrad_supported(k, M, N)
+        nws = ops.x3g_wgrad_workspace_floats(k, B, UH, UW, M, N)
+        assert nws == ops.h2g_wgrad_workspace_floats(k, B, UH, UW, M, N)          # the same pixel split
+        ws = torch.empty(nws, device='cuda')
+        if kind == 'CT':                                                           # M = Cin, N = Cout; dbias = sums of g (the S operand)
+            x = rnd(B, UH, UW, M); g = rnd(B, 2 * UH, 2 * UW, N) * 1e-2
+            dW3 = torch.full((M, N, 2, 2), float('nan'), device='cuda'); db3 = torch.full((N,), float('nan'), device='cuda')
+            dWh = torch.full_like(dW3, float('nan')); dbh = torch.full_like(db3, float('nan'))
+            ops.convt_x3_bwd_weight(x, g, dW3, ws, dbias=db3)
+            ops.convt_h2_bwd_weight(x, _slot(x), g, _slot(g), dWh, ws, dbias=dbh)
+            ref = torch.einsum('bhwi,bhawco->ioac', x.double(), g.double().reshape(B, UH, 2, UW, 2, N))
+        elif kind == 'S2':                                                         # M = Cout, N = Cin; dbias = sums of g (the U operand)
+            x = rnd(B, 2 * UH, 2 * UW, N); g = rnd(B, UH, UW, M) * 1e-2
+            dW3 = torch.full((M, N, 3, 3), float('nan'), device='cuda'); db3 = torch.full((M,), float('nan'), device='cuda')
+            dWh = torch.full_like(dW3, float('nan')); dbh = torch.full_like(db3, float('nan'))
+            ops.conv_s2_x3_bwd_weight(g, x, dW3, db3, ws)
+            ops.conv_s2_h2_bwd_weight(g, _slot(g), x, _slot(x), dWh, dbh, ws)
+            wref = torch.zeros(M, N, 3, 3, dtype=torch.float64, device='cuda', requires_grad=True)
+            F.conv2d(x.permute(0, 3, 1, 2).double(), wref, stride=2, padding=1).backward(g.permute(0, 3, 1, 2).double())
+            ref = wref.grad
+        else:                                                                      # M = Cout, N = C1 + C2 (two tensors); dbias = sums of g
+            x1 = rnd(B, UH, UW, N // 2); x2 = rnd(B, UH, UW, N // 2) * 5; g = rnd(B, UH, UW, M) * 1e-2
+            dW3 = torch.full((M, N), float('nan'), device='cuda'); db3 = torch.full((M,), float('nan'), device='cuda')
+            dWh = torch.full_like(dW3, float('nan')); dbh = torch.full_like(db3, float('nan'))
+            ops.conv1x1_x3_bwd_weight(g, M, x1, N // 2, x2, dW3, db3, ws)
+            ops.conv1x1_h2_bwd_weight(g, _slot(g), M, x1, _slot(x1), N // 2, x2, _slot(x2), dWh, dbh, ws)
+            ref = torch.einsum('bhwo,bhwi->oi', g.double(), torch.cat([x1, x2], 3).double())
+        print(f'{name}: dbias bf16x3 vs fp16x2 max |diff| {float((db3 - dbh).abs().max()):.3e}')
+        assert torch.isfinite(db3).all() and torch.equal(db3, dbh), name
+        _wgrad_check(f'{name} dW bf16x3', dW3, ref); _wgrad_check(f'{name} dW fp16x2', dWh, ref)
+        _wgrad_check(f'{name} dbias', dbh, g.double().sum((0, 1, 2)))

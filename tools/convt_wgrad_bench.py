@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Weight gradients of the pointwise / strided layers, bf16x3 (csrc/wgrad_x3g.hip) next to fp32-MFMA (csrc/wgrad.hip), at the shapes of
+"""Weight gradients of the pointwise / strided layers, bf16x3 (csrc/wgrad_g.h on the scheme of csrc/wgrad_x3g.hip) next to fp32-MFMA (csrc/wgrad.hip), at the shapes of
 config 3 (UNet: ConvTranspose2d upv6..9, B = 16) and config 5 (ResUnet: + stride-2 pool1..4 and 1x1 shortcuts sc6..9, B = 12)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
