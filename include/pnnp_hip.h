@@ -284,7 +284,7 @@ int pnnp_conv3x3_h2_bwd_weight_f32(const float* g, int g_cs, int Cout, const uns
 int pnnp_conv3x3_h2_bwd_data_res_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                      float* dx, int C1, const float* addsrc, const float* mask, int mode, unsigned* amax_dx,
                                      int B, int H, int W, void* stream);
-/* The same pointwise layers on the fp16 matrix cores (csrc/gemm_h2s.hip; round 5): the fp16x2 scheme of the 3x3 kernels (csrc/h2.h) -- per-tensor
+/* The same pointwise layers on the fp16 matrix cores (csrc/gemm_s.h on the scheme of csrc/gemm_h2s.hip; round 5): the fp16x2 scheme of the 3x3 kernels (csrc/h2.h) -- per-tensor
  * power-of-two scale from 4-byte amax slots, two fp16 pieces per operand, three products per multiply instead of bf16x3's six.  Contracts of the
  * _x3_ entries below + the slots: amax_x / amax_g of the tensor that is split on the fly, amax_w of the weight tensor (the kind-6 packs of
  * pnnp_pack_jobs_add_h2_convt / _1x1 / _s2 were scaled with it; pnnp_h2mat_bytes(K, N) bytes), amax_y / amax_dx (or null) raised to max |stored|.

@@ -7,7 +7,7 @@ int pnnp_igemm_launch(const IgemmArgs& a, int taps, int chan_per_seg, hipStream_
 int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);       // csrc/conv_x3.hip (3x3, bf16x3 split)
 int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);        // csrc/gemm_x3.hip (one tap per K segment, bf16x3 split)
 int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg);                        // its argument validation alone
-int pnnp_gemm_h2s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h2s.hip (the same GEMMs on the fp16x2 scheme)
+int pnnp_gemm_h2s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h2s.hip (the same GEMMs on the fp16x2 scheme; both: the kernel of csrc/gemm_s.h)
 
 namespace {
 
@@ -446,7 +446,7 @@ int gemm_h2_go(H2Args& h, int chan_per_seg, hipStream_t st) {
     if (rc != PNNP_OK) return rc;
     if (!pnnp_gemm_h2_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
     h.g.seg_channels = chan_per_seg;
-    h.g.chunks_per_seg = chan_per_seg / 32;                         // csrc/gemm_h2s.hip walks K in 32-channel items
+    h.g.chunks_per_seg = chan_per_seg / 32;                         // the fp16x2 scheme (csrc/gemm_h2s.hip) walks K in 32-channel items
     if ((int64_t)(h.g.Ntot / 32) * h.g.nseg * h.g.chunks_per_seg * 4096 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     return pnnp_gemm_h2s_launch(h, st);
 }

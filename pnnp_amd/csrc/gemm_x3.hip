@@ -1,5 +1,5 @@
 // Pointwise GEMMs (ConvTranspose2d k2 s2, Conv2d 1x1, stride-2 3x3: one tap per K segment) on the bf16 matrix cores: argument validation
-// and dispatch.  The kernel is csrc/gemm_x3s.hip (round 4: producer and consumer waves).  Round 3's kernel (32-channel items, every wave
+// and dispatch.  The kernel is csrc/gemm_s.h on the scheme of csrc/gemm_x3s.hip (round 4: producer and consumer waves).  Round 3's kernel (32-channel items, every wave
 // staging between its own MFMAs) lived in this file until round 5 (git history: gemm_x3_kernel; DESIGN Appendix A.1).
 #include "igemm.h"
 
@@ -32,6 +32,6 @@ int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s) {
     b.seg_channels = chan_per_seg;
     const int64_t wbytes = (int64_t)(a.Ntot / 32) * b.nseg * (chan_per_seg / 16) * WBLK;
     if (wbytes >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
-    b.chunks_per_seg = chan_per_seg / 16;                           // csrc/gemm_x3s.hip walks K in 16-channel items
+    b.chunks_per_seg = chan_per_seg / 16;                           // the bf16x3 scheme (csrc/gemm_x3s.hip) walks K in 16-channel items
     return pnnp_gemm_x3s_launch(b, s);
 }

@@ -110,7 +110,7 @@ __device__ __forceinline__ void x3_job(const PnnpPackJob& j, int64_t blk, int nb
     }
 }
 
-// bf16x3 pack of a K x N weight matrix for csrc/gemm_x3.hip:  dst (uint16) [Ntot/32][K16tot][octet 2][piece 3][32][8]
+// bf16x3 pack of a K x N weight matrix for csrc/gemm_x3.hip (csrc/gemm_s.h on the scheme of csrc/gemm_x3s.hip):  dst (uint16) [Ntot/32][K16tot][octet 2][piece 3][32][8]
 //   this job's sub-matrix: element (k, n), k < K, n < N  =  src[off + k*sk + n*sn], placed at row k_off + k (field `st`), column
 //   n_off + n of the whole matrix (K16tot = field T, Ntot = field Ndst).  Rows / columns no job covers must be zero-filled by the
 //   caller (the builders below cover everything).
@@ -135,7 +135,7 @@ __device__ __forceinline__ void x3mat_job(const PnnpPackJob& j, int64_t blk, int
     }
 }
 
-// fp16x2 pack of a K x N weight matrix for csrc/gemm_h2s.hip:  dst (fp16) [Ntot/32][K32tot][piece 2: hi', lo'][octet 4][32][8]  (4096 bytes per
+// fp16x2 pack of a K x N weight matrix for csrc/gemm_s.h on the scheme of csrc/gemm_h2s.hip:  dst (fp16) [Ntot/32][K32tot][piece 2: hi', lo'][octet 4][32][8]  (4096 bytes per
 //   32-channel item and 32-column block); sub-matrix addressing exactly as x3mat_job (K32tot = field T); W s with s = 2^pnnp_h2_scale_exp(*amax)
 //   of the WHOLE weight tensor (a kind-5 job), hi' = f16(W s), lo' = f16(W s - hi').  Rows / columns no job covers: zero-filled by the caller.
 __device__ __forceinline__ void h2mat_job(const PnnpPackJob& j, int64_t blk, int nblk) {

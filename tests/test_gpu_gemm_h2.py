@@ -1,5 +1,5 @@
-"""Pointwise layers on the fp16x2 scheme (csrc/gemm_h2s.hip): ConvTranspose2d(2, 2) forward / backward-data against float64 and against the exact
-bf16x3 kernels (csrc/gemm_x3s.hip), at the bars of tests/test_gpu_h2.py (the 3x3 kernels of the same scheme)."""
+"""Pointwise layers on the fp16x2 scheme (csrc/gemm_s.h + csrc/gemm_h2s.hip): ConvTranspose2d(2, 2) forward / backward-data against float64 and against the exact
+bf16x3 scheme (csrc/gemm_x3s.hip) of the same kernel, at the bars of tests/test_gpu_h2.py (the 3x3 kernels of the same scheme)."""
 import numpy as np
 import pytest
 import torch

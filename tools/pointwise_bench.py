@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Forward / backward-data of the layers that run on csrc/gemm_x3.hip, per layer: ConvTranspose2d upv6..9 (config 3, B = 16; config 5, B = 12),
+"""Forward / backward-data of the layers that run on the pointwise GEMM kernel (csrc/gemm_s.h; bf16x3 scheme: csrc/gemm_x3s.hip behind csrc/gemm_x3.hip), per layer: ConvTranspose2d upv6..9 (config 3, B = 16; config 5, B = 12),
 ResUnet's stride-2 convs pool1..4 and 1x1 shortcuts sc6..9 (B = 12).  ms, algorithmic TFLOP/s and the HBM floor of the layer at 5 TB/s.
---h2: the same layers on the fp16x2 kernel (csrc/gemm_h2s.hip); layers it does not take (N % 64) print nan."""
+--h2: the same layers on the fp16x2 scheme (csrc/gemm_h2s.hip); layers it does not take print nan."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
