@@ -352,7 +352,8 @@ int pnnp_conv3x3s2_x3_fwd_amax_f32(const float* x, int Cin, const void* w_x3, co
 int pnnp_conv3x3s2_x3_bwd_data_amax_f32(const float* g, int Cout, const void* w_x3_s2dgrad, float* dx, int Cin, const float* mask, int mode, int accum,
                                         unsigned* amax_dx /*or null*/, int B, int H, int W, void* stream);
 /* backward-weight of the same layers (csrc/wgrad_x3.hip; pixel-major LDS images read with ds_read_b64_tr_b16): same contract
- * as pnnp_conv_bwd_weight_f32 with taps = 9; channel counts in multiples of 32; workspace from the query. */
+ * as pnnp_conv_bwd_weight_f32 with taps = 9; channel counts in multiples of 32; workspace from the query.  A layer with 9 Cout Cin >= 2^31
+ * (8 GB per slab: no workspace holds it) is PNNP_E_UNSUPPORTED: the kernel indexes one slab with 32 bits. */
 int pnnp_x3_wgrad_supported(int H, int W, int Cout, int C1, int C2);
 /* its size limit: the WHOLE batch of a map [B][H][W][cstride] must fit a 32-bit byte offset ((B H + 2) W cstride 4 < 2^31) */
 int pnnp_x3_wgrad_fits(int B, int H, int W, int cstride);

@@ -7,6 +7,12 @@
 
 #define PNNP_WAVE 64
 
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
 static inline int pnnp_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PNNP_OK : PNNP_E_LAUNCH;

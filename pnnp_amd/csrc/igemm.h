@@ -20,10 +20,6 @@
 #pragma once
 #include "common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct IgemmSeg {
     const float* ptr;   // NHWC tensor [B][IH][IW][cstride]
     int cstride;        // channels per pixel of that tensor

@@ -10,26 +10,7 @@
 // wx3_reduce_kernel sums in a fixed order with alternating signs (deterministic, no float atomics; odd splits accumulate -G X so that the matrix
 // core's round-toward-minus-infinity accumulation cancels: DESIGN Appendix A.1b).  Round 2-3's kernel (8 waves, each a 32 x 32 x 9-tap
 // accumulator block and its own share of the staging) lived in this file until round 5 (git history: wgrad_x3_kernel).
-#include "common.h"
-#include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#ifndef WX3_ALT_SIGN
-#define WX3_ALT_SIGN 1
-#endif
-struct Wx3sArgs { const float* G; int Gcs; const float* X[2]; int Xcs[2]; int n_split; int B, H, W, M, N; float* slab; float* bias_slab; int Z; };
-int pnnp_wx3s_launch(const Wx3sArgs& a, hipStream_t s);           // csrc/wgrad_x3s.hip
-int pnnp_wx3s_th(int M, int N);                                     // its pixel-tile height for (M, N)
-struct Wh2sArgs { const float* G; int Gcs; const float* X[2]; int Xcs[2]; int n_split; int B, H, W, M, N; float* slab; float* bias_slab; int Z;
-                  const unsigned* amax_g; const unsigned* amax_x[2]; };
-int pnnp_wh2s_launch(const Wh2sArgs& a, hipStream_t s);           // csrc/wgrad_h2s.hip (fp16x2: same output tiles, same slabs, same reduce)
-int pnnp_wh2s_th(int M, int N);                                     // its (taller) pixel tiles
+#include "wgrad_s.h"
 
 namespace {
 
@@ -78,10 +59,9 @@ wx3_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int64
 // the surplus workgroups to whichever CU frees up first -- what keeps a weight gradient from doubling its time beside a resident collective
 // (round 5: VERDICT round 4, item 6a; the forward / backward-data grids do the same, csrc/capi.hip).  The slabs are still summed by INDEX in a
 // fixed order, so the result is deterministic for a given share; another share is another partition of the pixel sum (it differs by rounding).
-int wx3_splits(int B, int H, int W, int M, int N, int share) {
+int wx3_splits(int B, int H, int W, int M, int N, int th, int share) {
     const int bm = M % 64 == 0 ? 64 : 32, bn = N % 64 == 0 ? 64 : 32;
-    const int th = pnnp_wx3s_th(M, N);
-    const int tiles = ((W + 31) / 32) * ((H + th - 1) / th) * B;
+    const int tiles = ((W + 31) / 32) * ((H + th - 1) / th) * B;      // at most one split per pixel tile (th rows x 32 px) of the kernel that runs
     const int out_tiles = (M / bm) * (N / bn);
     int cus = pnnp_device_cus();
     if (cus <= 0) cus = 256;
@@ -118,15 +98,22 @@ int64_t pnnp_x3_wgrad_workspace_floats(int B, int H, int W, int Cout, int Cin) {
     if (Cout % 32 || Cin % 32) return 0;
     // sized for up to 4 workgroups per CU, whatever pnnp_set_persistent_split says when the caller asks (the engines size it once per shape)
     const int cur = pnnp_get_persistent_split();
-    return (int64_t)wx3_splits(B, H, W, Cout, Cin, cur > 4 ? cur : 4) * ((int64_t)9 * Cout * Cin + Cout);
+    // ... and with the bf16x3 tile heights, the shortest: never fewer splits than either scheme takes
+    return (int64_t)wx3_splits(B, H, W, Cout, Cin, pnnp_wx3s_th(Cout, Cin), cur > 4 ? cur : 4) * ((int64_t)9 * Cout * Cin + Cout);
 }
 
-// dW [Cout][C1+C2][3][3] (+ dbias [Cout]) of a 3x3 / stride 1 / pad 1 convolution; same contract as pnnp_conv_bwd_weight_f32
-// with taps = 9 (g: dL/d(pre-activation output), x1 / x2: the layer's input(s)).
-int pnnp_conv3x3_x3_bwd_weight_f32(const float* g, int g_cs, int Cout, const float* x1, int x1_cs, int C1,
-                                   const float* x2, int x2_cs, int C2, float* dW, float* dbias,
-                                   int B, int H, int W, int accumulate, float* workspace, int64_t workspace_floats, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// One host path for both schemes: validation, arguments, pixel splits, the scheme's kernel (launch / th: its launcher and its pixel-tile height), the reduce.
+// amax_*: the scaled scheme's slots (need_amax), null otherwise.
+int wx3_run(int (*launch)(const WsArgs&, hipStream_t), int (*th)(int, int), bool need_amax,
+            const float* g, int g_cs, int Cout, const unsigned* amax_g, const float* x1, int x1_cs, int C1, const unsigned* amax_x1,
+            const float* x2, int x2_cs, int C2, const unsigned* amax_x2, float* dW, float* dbias,
+            int B, int H, int W, int accumulate, float* workspace, int64_t workspace_floats, void* stream) {
     if (!g || !x1 || !dW || !workspace || B <= 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
+    if (need_amax && (!amax_g || !amax_x1 || (x2 && !amax_x2))) return PNNP_E_INVALID;
     const int N = C1 + (x2 ? C2 : 0);
     if (!pnnp_x3_wgrad_supported(H, W, Cout, C1, x2 ? C2 : 0)) return PNNP_E_UNSUPPORTED;
     if (g_cs < Cout || x1_cs < C1 || (x2 && x2_cs < C2) || (g_cs & 3) || (x1_cs & 3) || (x2 && (x2_cs & 3))) return PNNP_E_INVALID;
@@ -136,53 +123,39 @@ int pnnp_conv3x3_x3_bwd_weight_f32(const float* g, int g_cs, int Cout, const flo
     if (!pnnp_x3_wgrad_fits(B, H, W, cmax) || (x2 && !pnnp_x3_wgrad_fits(B, H, W, x2_cs))) return PNNP_E_UNSUPPORTED;
     if (workspace_floats < pnnp_x3_wgrad_workspace_floats(B, H, W, Cout, N)) return PNNP_E_WORKSPACE;
     hipStream_t st = as_stream(stream);
-    Wx3sArgs a{};
+    WsArgs a{};
     a.G = g; a.Gcs = g_cs;
     a.X[0] = x1; a.Xcs[0] = x1_cs; a.X[1] = x2 ? x2 : x1; a.Xcs[1] = x2 ? x2_cs : x1_cs; a.n_split = x2 ? C1 : (1 << 30);
     a.B = B; a.H = H; a.W = W; a.M = Cout; a.N = N;
-    a.Z = wx3_splits(B, H, W, Cout, N, pnnp_get_persistent_split());
+    a.Z = wx3_splits(B, H, W, Cout, N, th(Cout, N), pnnp_get_persistent_split());
     a.slab = workspace;
     a.bias_slab = dbias ? workspace + (int64_t)a.Z * 9 * Cout * N : nullptr;
-    const int rc = pnnp_wx3s_launch(a, st);
+    if (need_amax) { a.amax_g = amax_g; a.amax_x[0] = amax_x1; a.amax_x[1] = x2 ? amax_x2 : nullptr; }
+    const int rc = launch(a, st);
     if (rc != PNNP_OK) return rc;
-    const int64_t n = (int64_t)Cout * N * 9, ntot = n + (dbias ? Cout : 0);       // n % 32 == 0 (channels in multiples of 32)
-    hipLaunchKernelGGL(wx3_reduce_kernel, dim3((unsigned)((ntot + 31) / 32 > 4096 ? 4096 : (ntot + 31) / 32)), dim3(256), 0, st,
-                       a.slab, dW, n, a.Z, accumulate, (int64_t)Cout * N, 9, dbias ? a.bias_slab : nullptr, dbias, Cout);
-    return pnnp_launch_status();
+    return pnnp_wx3_reduce_launch(a.slab, dW, (int64_t)Cout * N, 9, a.Z, accumulate, a.bias_slab, dbias, Cout, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+// dW [Cout][C1+C2][3][3] (+ dbias [Cout]) of a 3x3 / stride 1 / pad 1 convolution on the bf16x3 kernel (csrc/wgrad_x3s.hip); same contract as
+// pnnp_conv_bwd_weight_f32 with taps = 9 (g: dL/d(pre-activation output), x1 / x2: the layer's input(s)).
+int pnnp_conv3x3_x3_bwd_weight_f32(const float* g, int g_cs, int Cout, const float* x1, int x1_cs, int C1,
+                                   const float* x2, int x2_cs, int C2, float* dW, float* dbias,
+                                   int B, int H, int W, int accumulate, float* workspace, int64_t workspace_floats, void* stream) {
+    return wx3_run(pnnp_wx3s_launch, pnnp_wx3s_th, false, g, g_cs, Cout, nullptr, x1, x1_cs, C1, nullptr, x2, x2_cs, C2, nullptr, dW, dbias,
+                   B, H, W, accumulate, workspace, workspace_floats, stream);
 }
 
 // The same weight gradient on the fp16 matrix cores (csrc/wgrad_h2s.hip, csrc/h2.h): both operands are split into two scaled fp16 pieces
-// on the fly, so each comes with its amax slot.  Same tiles, slabs, workspace and reduce as the bf16x3 kernel above.
+// on the fly, so each comes with its amax slot.  Same output tiles, slabs, workspace and reduce.
 int pnnp_conv3x3_h2_bwd_weight_f32(const float* g, int g_cs, int Cout, const unsigned* amax_g, const float* x1, int x1_cs, int C1, const unsigned* amax_x1,
                                    const float* x2, int x2_cs, int C2, const unsigned* amax_x2, float* dW, float* dbias,
                                    int B, int H, int W, int accumulate, float* workspace, int64_t workspace_floats, void* stream) {
-    if (!g || !x1 || !dW || !workspace || !amax_g || !amax_x1 || (x2 && !amax_x2) || B <= 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
-    const int N = C1 + (x2 ? C2 : 0);
-    if (!pnnp_x3_wgrad_supported(H, W, Cout, C1, x2 ? C2 : 0)) return PNNP_E_UNSUPPORTED;
-    if (g_cs < Cout || x1_cs < C1 || (x2 && x2_cs < C2) || (g_cs & 3) || (x1_cs & 3) || (x2 && (x2_cs & 3))) return PNNP_E_INVALID;
-    if ((((uintptr_t)g) | ((uintptr_t)x1) | ((uintptr_t)x2)) & 15) return PNNP_E_INVALID;
-    const int cmax = g_cs > x1_cs ? g_cs : x1_cs;
-    if (!pnnp_x3_wgrad_fits(B, H, W, cmax) || (x2 && !pnnp_x3_wgrad_fits(B, H, W, x2_cs))) return PNNP_E_UNSUPPORTED;
-    if (workspace_floats < pnnp_x3_wgrad_workspace_floats(B, H, W, Cout, N)) return PNNP_E_WORKSPACE;
-    hipStream_t st = as_stream(stream);
-    Wh2sArgs b{};
-    b.G = g; b.Gcs = g_cs; b.X[0] = x1; b.Xcs[0] = x1_cs; b.X[1] = x2 ? x2 : x1; b.Xcs[1] = x2 ? x2_cs : x1_cs; b.n_split = x2 ? C1 : (1 << 30);
-    b.B = B; b.H = H; b.W = W; b.M = Cout; b.N = N;
-    b.Z = wx3_splits(B, H, W, Cout, N, pnnp_get_persistent_split());      // (same output tiles: never more splits than the workspace was sized for)
-    {
-        const int th = pnnp_wh2s_th(Cout, N);
-        const int tiles = ((W + 31) / 32) * ((H + th - 1) / th) * B;    // ... and at most one per pixel tile of THIS kernel
-        if (b.Z > tiles) b.Z = tiles;
-    }
-    b.slab = workspace;
-    b.bias_slab = dbias ? workspace + (int64_t)b.Z * 9 * Cout * N : nullptr;
-    b.amax_g = amax_g; b.amax_x[0] = amax_x1; b.amax_x[1] = x2 ? amax_x2 : nullptr;
-    const int rc = pnnp_wh2s_launch(b, st);
-    if (rc != PNNP_OK) return rc;
-    const int64_t n = (int64_t)Cout * N * 9, ntot = n + (dbias ? Cout : 0);
-    hipLaunchKernelGGL(wx3_reduce_kernel, dim3((unsigned)((ntot + 31) / 32 > 4096 ? 4096 : (ntot + 31) / 32)), dim3(256), 0, st,
-                       b.slab, dW, n, b.Z, accumulate, (int64_t)Cout * N, 9, dbias ? b.bias_slab : nullptr, dbias, Cout);
-    return pnnp_launch_status();
+    return wx3_run(pnnp_wh2s_launch, pnnp_wh2s_th, true, g, g_cs, Cout, amax_g, x1, x1_cs, C1, amax_x1, x2, x2_cs, C2, amax_x2, dW, dbias,
+                   B, H, W, accumulate, workspace, workspace_floats, stream);
 }
 
 }  // extern "C"
