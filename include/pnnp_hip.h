@@ -183,7 +183,7 @@ int pnnp_pack_jobs_add_wino(PnnpPackJob* jobs, int* n, int cap, const float* w, 
 int pnnp_pack_jobs_add_conv3x3s2_dgrad(PnnpPackJob* jobs, int* n, int cap, const float* w, float* dst, int Cout, int Cin);
 
 /* ---- Conv2d 3x3 / stride 1 / pad 1 on the bf16 matrix cores with float32 operands split into three bf16 pieces
- * (csrc/conv_x3.hip: a = hi + mid + lo exactly, six of the nine piece products kept, fp32 accumulation -- float32-accurate
+ * (csrc/conv_x3s.hip: a = hi + mid + lo exactly, six of the nine piece products kept, fp32 accumulation -- float32-accurate
  * results at 6/16 of the fp32-MFMA time).  Same contracts as pnnp_conv_fwd_f32 / pnnp_conv_bwd_data_f32 /
  * pnnp_conv_bwd_data_res_f32 with taps = 9 (archs/Unet.py:16-52,54-92; archs/modules.py:176-197); the weights are x3 packs:
  * kind-2 jobs of the pack table, pnnp_x3_weight_bytes(K, N) bytes each (K = channels reduced over, N = channels written). */

@@ -14,7 +14,7 @@ from .. import ops
 class ConvPolicy:
     """Which kernel family a 3x3 layer runs on.
     ``x3``: forward / backward-data on the bf16 matrix cores with float32 operands split into three bf16 pieces
-    (csrc/conv_x3.hip: float32-accurate, 6/16 of the fp32-MFMA time) wherever the layer qualifies (reduction % 8 == 0,
+    (csrc/conv_x3s.hip: float32-accurate, 6/16 of the fp32-MFMA time) wherever the layer qualifies (reduction % 8 == 0,
     channels written % 32 == 0) -- the default;
     ``wino``: Winograd F(2x2,3x3) on the fp32 matrix cores for forward / backward-data where x3 is off and the layer
     qualifies (channels written % 64 == 0, reduction >= ``wino_mink`` channels), ``wino_wgrad``: the Winograd

@@ -556,7 +556,7 @@ class UNetEngine(_EngineBase):
                                                         amax_y=sl(name), bits_y=bits_of(name, hs[lvl], ws[lvl], ch[lvl])), name, fused=True)
                 a[f'p{i}'] = pooled
             elif s.fwd == 'x3+pool':
-                # conv{i}_2 writes the pooled map and the codes from its own epilogue (csrc/conv_x3.hip)
+                # conv{i}_2 writes the pooled map and the codes from its own epilogue (csrc/conv_x3s.hip)
                 a[f'c{i}'] = T.put(ops.conv_x3_fwd_pool(a[f'c{i}a'], None, self._wp[name][0], P[name + '.bias'],
                                                         g(name, (B, hs[lvl], ws[lvl], ch[lvl])), pooled, codes, ch[lvl], LRELU), name, fused=False)
                 a[f'p{i}'] = pooled

@@ -30,7 +30,7 @@ int pnnp_device_cus(void) {            // compute units of the CURRENT device (c
     return n >= 1 ? n : 256;           // MI355X
 }
 
-// How many workgroups the persistent forward / backward-data convolution kernels (csrc/conv_x3.hip, csrc/gemm_x3.hip) launch per CU.
+// How many workgroups the persistent forward / backward-data convolution kernels (csrc/conv_x3s.hip, csrc/gemm_x3.hip) launch per CU.
 // 1 (default): one workgroup per CU with an equal, static share of the tiles -- the fastest when the kernel has the chip to itself.
 // n > 1: n x CUs workgroups of 1/n share each; a CU still holds one at a time (160 KB of LDS), the others wait in the dispatcher and
 // go to whichever CU frees up first.  That is what makes running NEXT to another resident kernel safe (an RCCL collective on a side

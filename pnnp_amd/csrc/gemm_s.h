@@ -28,11 +28,11 @@ constexpr int NCW = 8, NPW = 4, NTHR = 64 * (NCW + NPW), PTHR = 64 * NPW;
 constexpr int MT = 2;                                              // pixel rows (of 32 px) per consumer wave
 constexpr unsigned OOB = 0x80000000u;
 #ifndef GEMMS_STORE_AUX
-#define GEMMS_STORE_AUX 2            // cache-policy bits of the epilogue's stores: 2 = nt (non-temporal, as in csrc/conv_x3s.hip: config 3 +0.3 %, config 5 +0.6 %,
+#define GEMMS_STORE_AUX 2            // cache-policy bits of the epilogue's stores: 2 = nt (non-temporal, as in csrc/conv_s.h: config 3 +0.3 %, config 5 +0.6 %,
                                    // three alternating same-box pairs: profiles/r4/ab_store_policy.txt)
 #endif
 #define GS_VMCNT(N) (0x0f70 | ((N) & 15) | (((N) >> 4) << 14))
-#define GS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      // (see csrc/conv_x3s.hip: not __syncthreads())
+#define GS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      // (see csrc/conv_s.h: not __syncthreads())
 
 template <class Scheme, int BN, int WN_> struct GCfg {
     static constexpr int WN = WN_;                                 // columns per consumer wave: 64 or 32
@@ -314,7 +314,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
     float amx0 = 0.f;                                                // max |stored value| of this lane, destination 0 (a.amax_out[0]; the launcher refuses [1])
     auto epilogue = [&](const Tile& tl) __attribute__((always_inline)) {
         const int b = tl.b;
-        // LEAN (Scheme::gen_lean(BN, WN)): the general epilogue on a register diet -- the lane number as an OPAQUE value (csrc/conv_h2s.hip: what is derived from it is computed
+        // LEAN (Scheme::gen_lean(BN, WN)): the general epilogue on a register diet -- the lane number as an OPAQUE value (csrc/conv_s_body.h: what is derived from it is computed
         // here, per tile, instead of being hoisted in front of the item loop and carried through it), one 32-column block's offsets and bias words at a time, one pixel
         // row of mask / residual / previous words in flight.  fp16x2's 128-column kernel needs it (it spilled without); bf16x3's kernels have the registers for
         // everything up front and both rows in flight (168, no spills), and were 2.5-5.7 % slower on the diet at ResUnet's 256^2 and 512^2 maps (stride-2 backward-data
@@ -390,7 +390,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
             return o;
         };
         // (scaled schemes) undoing the operand scales: x 2^dexp (exact) as one multiplier while 2^dexp is a normal float32; tensors so small / large that it is
-        // not first take the remainder in a pass over the accumulators (csrc/conv_h2s.hip)
+        // not first take the remainder in a pass over the accumulators (csrc/conv_s_body.h)
         float dsc = 1.f;
         if constexpr (Scheme::SCALED) {
             const int dexp = -(se_x + se_w);
@@ -414,7 +414,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
         };
         if constexpr (EK != EK_GEN) {
             constexpr bool MASKED = EK == EK_BWD, BITS = EK == EK_BWDB;
-            // FULL-LINE memory pattern (csrc/conv_x3s.hip): the two 16-column blocks of a 32-column block trade halves between lanes p and p + 8
+            // FULL-LINE memory pattern (csrc/conv_s_body.h): the two 16-column blocks of a 32-column block trade halves between lanes p and p + 8
             // of a 16-lane row, so that each 16-byte store instruction writes 8 pixels x 128 bytes (whole lines) instead of 16 x 64; the
             // act' masks come in by the same pattern and are traded back.
             const bool lo8 = p16 < 8;
@@ -484,7 +484,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
                     for (int h = 0; h < 2; ++h) {
                         f32x4 o0, o1;
                         if constexpr (BITS) {
-                            // scale and mask in three instructions per element (csrc/conv_h2s.hip mask_scale): next bit -> vcc, 2^dexp or msl 2^dexp, multiply
+                            // scale and mask in three instructions per element (csrc/conv_s_body.h mask_scale): next bit -> vcc, 2^dexp or msl 2^dexp, multiply
                             const f32x4 v0 = raw(2 * i + h, 2 * k), v1 = raw(2 * i + h, 2 * k + 1);
                             const float fneg = dsc * msl;
                             auto ms = [&](float v) __attribute__((always_inline)) {

@@ -29,20 +29,21 @@ __host__ __device__ inline int pnnp_h2_scale_exp(unsigned amax_bits) {
 }
 
 struct H2Args {
-    IgemmArgs g;                             // geometry, sources, destinations, fp32 masks: as for the bf16x3 kernels
+    IgemmArgs g;                             // geometry, sources, destinations, fp32 masks: as for the bf16x3 kernels (whose kernel, csrc/conv_x3s.hip, takes this
+                                             // struct too, with every field below null or zero: one kernel text, csrc/conv_s_body.h)
     const unsigned* amax_in[2];              // amax slot of K segment 0 / 1 (the tensors that are split on the fly); [1] null without a second segment
     const unsigned* amax_w;                  // amax slot of the weight tensor (the pack was scaled with it: csrc/pack_jobs.hip kind 4)
     unsigned* amax_out[2];                   // max|stored value| per destination (or null)
     unsigned* bits_out;                      // forward: sign bits of the stored (activated) output, tile-private layout (or null)
     const unsigned* bits_in[2];              // backward-data: act' mask of destination 0 / 1 as bits written by the forward kernel (or null)
     int bits_nblk[2];                        // 32-channel blocks of the tensor behind bits_out ([0]) / bits_in[du]
-    // forward layer + the network's 1x1 head in ONE kernel (csrc/conv_h2s.hip EK_HEAD; Ntot == 32): head_out NCHW [B][4][OH][OW] = head_w [4][32] . act(y) + head_b
+    // forward layer + the network's 1x1 head in ONE kernel (csrc/conv_s.h EK_HEAD; Ntot == 32): head_out NCHW [B][4][OH][OW] = head_w [4][32] . act(y) + head_b
     // (+ head_res, NCHW like head_out); g.dst[0] may then be null (the 32-channel map is not stored).  head_out null: an ordinary launch.
     const float* head_w; const float* head_b; const float* head_res; float* head_out;
-    // split-K for small grids (csrc/conv_h2s.hip): ksplit > 1 workgroups share an output tile, each walking 1 / ksplit of the K chunks and writing raw partial
+    // split-K for small grids (csrc/conv_s_body.h, csrc/conv_h2s.hip): ksplit > 1 workgroups share an output tile, each walking 1 / ksplit of the K chunks and writing raw partial
     // sums to image ks B + b of g.dst[0] = a [ksplit][B][OH][OW][cs] slab tensor (general epilogue, no bias / activation / mask / bits); 0 or 1: off
     int ksplit;
-    // backward-data into a tensor that was max-pooled as well (csrc/conv_h2s.hip EK_BWDU): the gradient of the pooled map [B][OH/2][OW/2][g.pool_cs] and the
+    // backward-data into a tensor that was max-pooled as well (csrc/conv_s.h EK_BWDU): the gradient of the pooled map [B][OH/2][OW/2][g.pool_cs] and the
     // codes pnnp_maxpool2_fwd_codes_f32 / the pooled forward wrote; the epilogue adds the un-pooled term before the store.  Both null: an ordinary launch.
     const float* unpool_g; const unsigned char* unpool_codes;
     // a backward-data launch without any mask (a column range of a decoder layer: the gradient of the up-sampled half): take the bit-masked backward-data

@@ -30,7 +30,7 @@ struct IgemmSeg {
 struct IgemmArgs {
     IgemmSeg seg[9];               // up to 9 K segments (a stride-2 3x3 conv is 9 strided 1x1 taps)
     int nseg, chunks_per_seg;      // K = nseg * chunks_per_seg * KC channels (x TAPS)
-    int seg_channels;              // (csrc/conv_x3.hip) channels a segment contributes; its last 16-channel chunk may be half empty
+    int seg_channels;              // (csrc/conv_x3s.hip) channels a segment contributes; its last 16-channel chunk may be half empty
     int in_mul, IH, IW;
     int B, DH, DW;                 // tile domain (what M iterates over)
     const float* w;                // packed [TAPS][Ktot/4][Ntot][4]
@@ -46,7 +46,7 @@ struct IgemmArgs {
     int mask_mode[2];              // 0 none, 1 x lrelu'(mask), 2 x relu'(mask)
     int accum[2];                  // dst += result
     const float* addsrc;           // optional residual tensor with dst[0] geometry, added before act (or null)
-    // (csrc/conv_x3.hip, forward only) MaxPool2d(2) of the activated output fused into the epilogue: the pooled map
+    // (csrc/conv_x3s.hip, forward only) MaxPool2d(2) of the activated output fused into the epilogue: the pooled map
     // [B][OH/2][OW/2][pool_cs] and the one-byte argmax + sign codes of pnnp_maxpool2_fwd_codes_f32 (or both null)
     float* pool_dst;
     unsigned char* pool_codes;

@@ -4,7 +4,7 @@
 // argument, <= 32 per launch) and every workgroup finds its job from a prefix of block counts.
 //   job kind 0: strided gather  dst[((t*(K/4)+kq)*Ndst + n_off + n)*4 + kr] = src[off + k*sk + n*sn + ts*st]  (k < Kvalid else 0)
 //   job kind 1: Winograd filter transform into the kernel's chunked order (csrc/wino.hip)
-//   job kind 2: 3x3 filters split into three bf16 pieces in the order csrc/conv_x3.hip streams them by LDS-DMA
+//   job kind 2: 3x3 filters split into three bf16 pieces in the order csrc/conv_x3s.hip streams them by LDS-DMA
 //   job kind 3: a strided K x N matrix (1x1 / ConvTranspose / strided-tap weights) split likewise for csrc/gemm_x3.hip
 //   job kind 4: 3x3 filters scaled by a power of two and split into two fp16 pieces for csrc/conv_h2s.hip (the scale comes from the amax slot
 //               that a kind-5 job of an EARLIER launch filled)
@@ -71,7 +71,7 @@ __device__ __forceinline__ void wino_job(const PnnpPackJob& j, int64_t blk, int 
     }
 }
 
-// bf16x3 pack of a 3x3 Conv2d weight for csrc/conv_x3.hip:  dst (uint16) [N/32][K16][tap 9][octet 2][piece 3][32][8]
+// bf16x3 pack of a 3x3 Conv2d weight for csrc/conv_x3s.hip:  dst (uint16) [N/32][K16][tap 9][octet 2][piece 3][32][8]
 //   element (k = chunk*16 + octet*8 + e, n = nb*32 + nn, tap):  forward  W = w[n][k][tap]        (K = Cin, N = Cout)
 //                                                               dgrad    W = w[k][n][8 - tap]    (K = Cout, N = Cin)
 //   pieces hi = bf16(W), mid = bf16(W - hi), lo = bf16(W - hi - mid) (round to nearest even; W = hi + mid + lo exactly);
@@ -326,7 +326,7 @@ int pnnp_pack_jobs_add_wino(PnnpPackJob* jobs, int* n, int cap, const float* w, 
     return ok ? PNNP_OK : PNNP_E_WORKSPACE;
 }
 
-// bf16x3 packs of a 3x3 Conv2d weight for the pnnp_conv3x3_x3_* kernels (csrc/conv_x3.hip): fwd (K = Cin padded to Cin_pad, a
+// bf16x3 packs of a 3x3 Conv2d weight for the pnnp_conv3x3_x3_* kernels (csrc/conv_x3s.hip): fwd (K = Cin padded to Cin_pad, a
 // multiple of 16; N = Cout) and / or dgrad (K = Cout padded up to a multiple of 16; N = Cin).  N is padded up to a multiple of
 // 32 inside the pack (zeros).  Sizes: pnnp_x3_weight_bytes.
 int pnnp_pack_jobs_add_x3(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, void* dgrad, int Cout, int Cin, int Cin_pad) {

@@ -1,5 +1,5 @@
 // Weight gradients of the POINTWISE / STRIDED layers on the bf16 matrix cores: the kernel of csrc/wgrad_g.h (geometries, tiles, staging layout, slabs)
-// on the bf16x3 scheme of csrc/conv_x3.hip and csrc/wgrad_x3.hip (round 4).  Both operands are split into THREE bf16 pieces on the way into LDS, unscaled;
+// on the bf16x3 scheme of csrc/conv_x3s.hip and csrc/wgrad_x3.hip (round 4).  Both operands are split into THREE bf16 pieces on the way into LDS, unscaled;
 // a (tap, 32 x 32 block) is SIX v_mfma_f32_32x32x16_bf16; a staging slice is 11 steps of 2-4 VALU instructions.
 #include "x3.h"
 #include "wgrad_g.h"

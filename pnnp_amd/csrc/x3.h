@@ -1,5 +1,5 @@
 // The bf16x3 ("x3") family's operand split: a float32 value as the sum of three bf16 pieces hi + mid + lo (round to nearest even each; the residuals
-// are exact in float32), two values per register (csrc/conv_x3.hip).
+// are exact in float32), two values per register (csrc/conv_x3s.hip).
 #pragma once
 #include "common.h"
 

@@ -112,7 +112,7 @@ class PackJobs:
         self.keep += [w, fwd, dgrad]
 
     def add_x3(self, w, fwd, dgrad, cin_pad=None):
-        """bf16x3 packs (csrc/conv_x3.hip) of a 3x3 Conv2d weight; fwd / dgrad: uint8 buffers of x3_weight_bytes, or None."""
+        """bf16x3 packs (csrc/conv_x3s.hip) of a 3x3 Conv2d weight; fwd / dgrad: uint8 buffers of x3_weight_bytes, or None."""
         co, ci = w.shape[0], w.shape[1]
         check(_prep().pnnp_pack_jobs_add_x3(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci,
                                             cin_pad or (ci + 15) // 16 * 16), 'pack_jobs_add_x3')

@@ -474,7 +474,7 @@ def test_wide_h2_splitk():
 
 
 # --------------------------------------------------------------------------------------------------------------------- the bf16x3 family (the range tripwire's fallback)
-# conv_x3.hip asks the same width rule (pnnp_conv3_tile_columns, csrc/igemm.h), so ops.h2_tile_columns answers for these launches too.
+# conv_x3s.hip asks the same width rule (pnnp_conv3_tile_columns, csrc/igemm.h), so ops.h2_tile_columns answers for these launches too.
 @pytest.mark.parametrize('case', WIDE_CASES, ids=IDS)
 def test_wide_x3_fwd(case):
     from pnnp_amd import ops

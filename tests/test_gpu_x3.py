@@ -1,4 +1,4 @@
-"""GPU parity of the bf16x3 convolution kernels (csrc/conv_x3.hip: float32 operands split into three bf16 pieces on the
+"""GPU parity of the bf16x3 convolution kernels (csrc/conv_x3s.hip: float32 operands split into three bf16 pieces on the
 bf16 matrix cores) against torch-fp32 CPU references of the same op -- at the SAME tolerances as the fp32-MFMA kernels
 (tests/test_gpu_conv.py: rtol 1e-4 / atol 1e-5 of the largest sum) -- and, to show the split is not a precision loss,
 against a float64 reference next to the fp32-MFMA kernel's own error."""

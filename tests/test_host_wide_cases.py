@@ -1,5 +1,5 @@
 """Why tests/test_gpu_wide_tiles.py exists, without a GPU: the tile width of the fp16x2 / bf16x3 3x3 kernels is a host function of the launch's shape
-(pnnp_h2_tile_columns; csrc/conv_x3.hip asks the same helper, csrc/igemm.h), and the benchmark's layers resolve to 64 columns while the shape list the
+(pnnp_h2_tile_columns; csrc/conv_x3s.hip asks the same helper, csrc/igemm.h), and the benchmark's layers resolve to 64 columns while the shape list the
 reference tests share (tests/test_gpu_x3.py::CASES) resolves to 32.  If the width rule changes, this file tells which reference tests have stopped
 covering the instantiation the benchmark runs."""
 import ctypes

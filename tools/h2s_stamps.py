@@ -1,4 +1,4 @@
-"""With a library built with -DH2S_STAMPS (tools/build_variant.sh h2st conv_h2s.hip -DH2S_STAMPS; PNNP_LIB=...): per-wave cycle sums of
+"""With a library built with -DCONVS_STAMPS (tools/build_variant.sh h2st conv_h2s.hip -DCONVS_STAMPS; PNNP_LIB=...): per-wave cycle sums of
 igemm_h2s_kernel on one 3x3 layer (B = 16), per chunk.   usage: h2s_stamps.py S Cin Cout [fwd|fwdres|dgrad|dgradf]   (fwdres: forward with a residual = the general epilogue; dgradf: float32 masks)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

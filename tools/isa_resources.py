@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / scratch / LDS table of the library's HIP sources.
 
-    python tools/isa_resources.py [file.hip ...] [--flags "-DH2S_NSETS=3"] [--all] > profiles/r6/isa_resources.txt
+    python tools/isa_resources.py [file.hip ...] [--flags "-DCONVS_STORE_AUX=0"] [--all] > profiles/r6/isa_resources.txt
 
 Compiles each source with the flags tools/build.py uses plus -Rpass-analysis=kernel-resource-usage (hipcc cross-compiles: no GPU
 needed) and prints one line per kernel instantiation.  `sgpr_spill` are scalar registers parked in vector-register LANES

@@ -22,7 +22,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--only', default='fwd,dgrad,wgrad')
     ap.add_argument('--layers', default='')
-    ap.add_argument('--x3', action='store_true', help='bf16x3 kernels (csrc/conv_x3.hip) for fwd / dgrad')
+    ap.add_argument('--x3', action='store_true', help='bf16x3 kernels (csrc/conv_x3s.hip) for fwd / dgrad')
     ap.add_argument('--h2', action='store_true', help='fp16x2 kernels (csrc/conv_h2s.hip) for fwd / dgrad (dgrad masks as sign bits; --h2-fmask: as float32)')
     ap.add_argument('--h2-fmask', action='store_true')
     a = ap.parse_args()

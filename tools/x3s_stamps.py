@@ -1,4 +1,4 @@
-"""With a library built with -DX3S_STAMPS: per-wave cycle sums of igemm_x3s_kernel on one 3x3 layer (B = 16), per chunk (= 3 items).
+"""With a library whose conv_x3s.hip was built with -DCONVS_STAMPS (tools/build_variant.sh x3st conv_x3s.hip -DCONVS_STAMPS; PNNP_LIB=...): per-wave cycle sums of igemm_x3s_kernel on one 3x3 layer (B = 16), per chunk (= 3 items).
 usage: x3s_stamps.py S Cin Cout [fwd|dgrad]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
