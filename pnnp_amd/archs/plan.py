@@ -161,6 +161,15 @@ def _convt_wgrad(pol, h2, B, ci, co, H, W, lvl, slots=True):
     return 'h2' if (h2 and pol.h2_pointwise and slots) else 'x3'
 
 
+def _pointwise_family(pol, kf, nf, kd, nd, h2=True):
+    """A ConvTranspose2d or stride-2 3x3 layer on the pointwise GEMM kernels: its forward is a GEMM with K = kf, N = nf, its backward-data one with
+    K = kd, N = nd.  bf16x3 where both have a tile, fp16x2 (``h2``: the layer's operands carry amax slots) where it would take what bf16x3 takes,
+    else the direct kernels."""
+    if not (pol.use_x3_pointwise(kf, nf) and pol.use_x3_pointwise(kd, nd)):
+        return 'direct'
+    return 'h2' if (h2 and pol.h2 and pol.h2_pointwise and ops.gemm_h2_supported(kf, nf) and ops.gemm_h2_supported(kd, nd)) else 'x3'
+
+
 def resolve_unet(ch, cin, cout, pol, train, B, H, W):
     """UNetSeeInDark: conv{1..9}_{1,2} (3x3), upv{6..9} (ConvTranspose2d 2x2 s2), conv10_1 (1x1 head)."""
     cin_pad = _pad8(cin)
@@ -175,11 +184,7 @@ def resolve_unet(ch, cin, cout, pol, train, B, H, W):
             st[name] = Step(*_conv3_packs(pol, ch[lvl], cip, ci, c1, train and name != 'conv1_1'))
         if i >= 6:
             ci, co = ch[lvl + 1], ch[lvl]
-            if (pol.h2 and pol.h2_pointwise and pol.use_x3_pointwise(ci, 4 * co) and pol.use_x3_pointwise(co, ci)
-                    and ops.gemm_h2_supported(ci, 4 * co) and ops.gemm_h2_supported(co, ci)):
-                f = 'h2'
-            else:
-                f = 'x3' if pol.use_x3_pointwise(ci, 4 * co) and pol.use_x3_pointwise(co, ci) else 'direct'
+            f = _pointwise_family(pol, ci, 4 * co, co, ci)
             st[f'upv{i}'] = Step(f, f if train else None)
     thin_head = pol.use_thin_head(ch[0], cout, B * H * W)
     st['conv10_1'] = Step('thin' if thin_head else 'direct', ('thin' if thin_head else 'direct') if train else None, pack=('direct', 'direct' if train else None))
@@ -246,21 +251,13 @@ def resolve_resunet(ch, cin, cout, pol, train, B, H, W):
         if i >= 6:
             st[f'sc{i}'] = Step(*(_pointwise_packs(pol, 2 * c, c, c, train) or ('direct', 'direct' if train else None)))
     for i in range(1, 5):                  # (the engine packs in the order of the steps)
-        ci, co = ch[i - 1], ch[i]
-        if pol.h2 and pol.h2_pointwise and pol.use_x3_pointwise(ci, co) and ops.gemm_h2_supported(ci, co) and ops.gemm_h2_supported(co, ci):
-            f = 'h2'
-        else:
-            f = 'x3' if pol.use_x3_pointwise(ci, co) and pol.use_x3_pointwise(co, ci) else 'direct'
+        f = _pointwise_family(pol, ch[i - 1], ch[i], ch[i], ch[i - 1])
         st[f'pool{i}'] = Step(f, f if train else None)
     for i in range(6, 10):
         lv = 9 - i
         ci, co = ch[lv + 1], ch[lv]
         # (only beside an fp16x2 shortcut: its backward-data leaves the amax slot of the summed gradient this layer's backward splits)
-        if (pol.h2 and pol.h2_pointwise and st[f'sc{i}'].fwd == 'h2' and pol.use_x3_pointwise(ci, 4 * co)
-                and ops.gemm_h2_supported(ci, 4 * co) and ops.gemm_h2_supported(co, ci)):
-            f = 'h2'
-        else:
-            f = 'x3' if pol.use_x3_pointwise(ci, 4 * co) and pol.use_x3_pointwise(co, ci) else 'direct'
+        f = _pointwise_family(pol, ci, 4 * co, co, ci, h2=st[f'sc{i}'].fwd == 'h2')
         st[f'upv{i}'] = Step(f, f if train else None)
     head = _pointwise_packs(pol, ch[0], cout, None, train) or ('direct', 'direct' if train else None)
     thin_head = pol.use_thin_head(ch[0], cout, B * H * W)

@@ -367,7 +367,7 @@ class HipTrainStep:
         pred = e.forward(noisy, True)
         bufs = e.bufs[(B, H, W, dev)]
         # dL/d(out), NHWC: 4 channels when the 1x1 head's backward runs on the streaming kernel (it reads gcs >= 4), zero-padded to 8 for the GEMM kernels
-        gch = e.grad_out_channels(B, H, W) if hasattr(e, 'grad_out_channels') else e.cout_pad
+        gch = e.grad_out_channels(B, H, W)
         g8 = bufs.get('g_out8' if gch == e.cout_pad else 'g_out4', (B, H, W, gch), dev)
         loss = bufs.get('loss_out', (1 + B,), dev)
         lws = bufs.get('loss_ws', (128 * B,), dev)

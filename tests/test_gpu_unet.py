@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_host_plan import FAMILIES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -96,34 +98,54 @@ def test_unet_nf32_full_crop_golden(golden_dir):
     np.testing.assert_allclose(y.double().sum(dim=(0, 2, 3)).cpu().numpy(), g['chan_sum'], rtol=1e-4)
 
 
-def test_unet_nf32_train_vs_oracle_and_eval_shapes():
-    """nf=32, B=2 96x160 crops: loss + all parameter gradients vs the torch-fp32 oracle
-    (rel. L2 error < 2e-3 per tensor: the L1 sign, max-pool argmax and LeakyReLU masks are
-    discontinuous, so last-bit forward differences flip a few of them); then a ragged eval shape (not a multiple of 32 wide)."""
+# kernel-family policies the nf = 32 oracle tests run under (this file and tests/test_gpu_resunet.py): the four families and the fp16x2
+# family with one sub-switch off -- between them every branch of the engines' per-family layer calls (archs/engine.py) is taken
+POLICIES = dict(FAMILIES, **{'h2-x3pointwise': dict(FAMILIES['h2'], h2_pointwise=False), 'h2-x3wgrad': dict(FAMILIES['h2'], h2_wgrad=False),
+                             'h2-nothin': dict(FAMILIES['h2'], thin=False)})
+UNET_POLICIES = dict(POLICIES, **{'h2-nopoolfused': dict(FAMILIES['h2'], pool_fused=False), 'h2-nounpoolfused': dict(FAMILIES['h2'], unpool_fused=False),
+                                  'h2-noheadfused': dict(FAMILIES['h2'], head_fused=False)})
+
+
+@pytest.fixture(scope='module')
+def unet_nf32_oracle():
+    """weights, inputs and the torch-fp32 oracle's loss, gradients and eval output: computed once for every policy"""
     from oracle import net_torch as O
     from pnnp_amd.archs import UNetSeeInDark, initialize_weights
-    from pnnp_amd.trainer import HipTrainStep
     torch.manual_seed(3)
     net = UNetSeeInDark(dict(nframes=1, res=False, nf=32, in_nc=4, out_nc=4))
     initialize_weights(net)
     sd = {k: v.detach().clone() for k, v in net.state_dict().items()}
-    net = net.cuda()
     x = torch.rand(2, 4, 96, 160); t = torch.rand(2, 4, 96, 160)
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
     loss_ref = O.l1_clamp_loss(O.unet_forward(leaves, x), t)
     loss_ref.backward()
-    ts = HipTrainStep(net, lr=0.0, clip=0)
-    lo = ts.step(t.cuda(), noisy=x.cuda())
-    assert abs(float(lo[0]) - loss_ref.item()) < 2e-6
-    for k, p in net.named_parameters():
-        got = net.engine.params.grad_view(k, p.shape).cpu()
-        ref = leaves[k].grad
-        rel = float((got - ref).norm() / (ref.norm() + 1e-12))
-        assert rel < 2e-3, (k, rel)
     xe = torch.rand(1, 4, 48, 112)
     with torch.no_grad():
-        ye = net(xe.cuda())
         yr = O.unet_forward(sd, xe)
+    return sd, x, t, loss_ref.item(), {k: v.grad for k, v in leaves.items()}, xe, yr
+
+
+@pytest.mark.parametrize('policy', list(UNET_POLICIES))
+def test_unet_nf32_train_vs_oracle_and_eval_shapes(unet_nf32_oracle, policy):
+    """nf=32, B=2 96x160 crops: loss + all parameter gradients vs the torch-fp32 oracle
+    (rel. L2 error < 2e-3 per tensor: the L1 sign, max-pool argmax and LeakyReLU masks are
+    discontinuous, so last-bit forward differences flip a few of them); then a ragged eval shape (not a multiple of 32 wide)."""
+    from pnnp_amd.archs import UNetSeeInDark
+    from pnnp_amd.trainer import HipTrainStep
+    sd, x, t, loss_ref, grads, xe, yr = unet_nf32_oracle
+    net = _load(UNetSeeInDark(dict(nframes=1, res=False, nf=32, in_nc=4, out_nc=4)), sd)
+    net.engine.set_policy(**UNET_POLICIES[policy])
+    ts = HipTrainStep(net, lr=0.0, clip=0)
+    lo = ts.step(t.cuda(), noisy=x.cuda())
+    rels = {k: float((net.engine.params.grad_view(k, p.shape).cpu() - grads[k]).norm() / (grads[k].norm() + 1e-12)) for k, p in net.named_parameters()}
+    worst = max(rels, key=rels.get)
+    print(f'unet nf32 {policy}: loss diff {abs(float(lo[0]) - loss_ref):.3e}, worst gradient {worst} rel L2 {rels[worst]:.3e}')
+    assert abs(float(lo[0]) - loss_ref) < 2e-6
+    for k, rel in rels.items():
+        assert rel < 2e-3, (k, rel)
+    with torch.no_grad():
+        ye = net(xe.cuda())
+    print(f'unet nf32 {policy}: eval max abs diff {float((ye.cpu() - yr).abs().max()):.3e}')
     np.testing.assert_allclose(ye.cpu().numpy(), yr.numpy(), rtol=1e-4, atol=2e-6)
 
 
