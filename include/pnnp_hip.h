@@ -570,6 +570,25 @@ int pnnp_nf_train_bwd_pair_f32(const float* x, const float* clean /*or null*/, c
 int pnnp_nf_train_stats_f32(const float* u, const float* ident, const float* prm, float* bn, float* h1, float* h2, float* part,
                             int B, int H, int W, void* stream);
 
+/* ---------------------------------------------------------------- NoiseFlow.sample backward (csrc/nf_sample_bwd.hip)
+ * The vector-Jacobian product of one [AffineCoupling^-1, Conv2d1x1^-1] pair of the reversed chain that pnnp_nf_step(_mix)_f32 runs:
+ *   out = (Winv [u0, u1, (u2 - shift_a) exp(-ls_a), (u3 - shift_b) exp(-ls_b)]) * s,   (shift, ls) = coupling_net(u[0:2]),
+ *   s = sqrt(a*clean + b) with clean (last pair), else 1.
+ * All pointers are DEVICE pointers.  The caller keeps each pair's input u; the hidden maps are recomputed here.
+ *   u, dout     [B][4][H][W] the pair's input and the gradient of its output;  du: gradient of its input (aliases neither)
+ *   winv [4][4] the Conv2d1x1 inverse (x the GainISO scalar where it applies);  ab {a, b};  prm [301] as for pnnp_nf_train_*
+ *   bn [24]     mean1[4] rstd1[4] -[4] mean2[4] rstd2[4] -[4] of the BIAS-FREE conv outputs.  bn_batch = 1: the batch statistics
+ *               pnnp_nf_train_stats_f32 left for the forward (training mode; the BatchNorm-backward statistics terms are carried);
+ *               bn_batch = 0: a fixed affine, mean = running_mean - conv bias, rstd = 1/sqrt(running_var + eps) (eval mode)
+ *   gprm [301]  gradient of prm, same layout;  dwinv [16];  dab [2] (required with clean, else unused)
+ *   scratch     h1, h2, out3, dy2, dy1 [B][4][H][W] each;  sums [319];  part [pnnp_nf_sample_bwd_part_floats(B,H,W)]
+ * Deterministic (no float atomics): per-workgroup partial rows, then a column reduction in double. */
+int64_t pnnp_nf_sample_bwd_part_floats(int B, int H, int W);
+int pnnp_nf_sample_bwd_pair_f32(const float* u, const float* clean /*or null*/, const float* ab, const float* winv, const float* prm,
+                                const float* bn, int bn_batch, const float* dout, float* du, float* gprm, float* dwinv,
+                                float* dab /*or null*/, float* h1, float* h2, float* out3, float* dy2, float* dy1, float* sums,
+                                float* part, int B, int H, int W, void* stream);
+
 /* SNA_torch (data_process/process.py:562-588): shot-noise augmentation under a white-balance gain change.
  * gt [C][H][W] -> dn (the extra Poisson noise, / (wp-bl), x ratio unless ori) and dy (the signal change); aug_wb4 is a
  * HOST array of the four plane gains.  Counter-based RNG as in pnnp_noise_sample_f32. */

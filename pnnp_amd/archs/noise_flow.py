@@ -11,6 +11,9 @@ Fitting the flow (trainer_NF_SID.py:102,116-126: ``net.train(); nll, _ = net.los
 works unchanged: in training mode ``loss()`` runs the chain with batch statistics on the kernels of csrc/nf_train.hip and
 returns an autograd-connected scalar whose ``backward()`` runs the hand-written backward kernels and fills ``.grad`` of every
 trainable parameter.  Only the 4x4 / scalar parameter algebra (W = P L U, the ISO tables) is left to torch autograd.
+
+Fitting it on a distribution loss of its own samples (utils/kld_div.py:56-74) goes through ``sample(..., differentiable=True)``:
+the same values with the backward kernels of csrc/nf_sample_bwd.hip behind them (``_SampleChain``), the same split of the algebra.
 """
 import ctypes as C
 
@@ -203,6 +206,72 @@ class _PairChainNLL(torch.autograd.Function):
         dab = sums[net._sdn_pair, o3 + 92:o3 + 94].clone() if net._sdn_pair is not None else torch.zeros(2, **f32)
         dnoise = dz if ctx.needs_input_grad[1] else None
         return (None, dnoise, None, dw, dab) + tuple(cg)
+
+
+class _SampleChain(torch.autograd.Function):
+    """NoiseFlow.sample(differentiable=True): the values of ``sample()`` (the same kernel launches, each pair's input kept instead of
+    ping-ponged) with the hand-written backward of csrc/nf_sample_bwd.hip behind them.
+
+    Inputs that carry gradients: z (the prior draw, when injected), wstack [P,4,4] (the Conv2d1x1 matrices W = P L U in the order of
+    the reversed chain, divided by the GainISO scalar on the pair that carries it), ab [2] (signal-dependent scale) and the 12
+    parameters of each coupling.  The kernels work with the numeric inverses the host tables hold; the gradient handed back for
+    wstack is dW = -Winv^T (dWinv) Winv^T, so no device-side matrix inverse is needed."""
+
+    @staticmethod
+    def forward(ctx, net, kw, z, wstack, ab, *cparams):
+        keep = {'u': [], 'winv': [], 'sdn': []}
+        out = net._sample_run(dict(kw, z=z, _keep=keep))
+        P = len(keep['u'])
+        dev = out.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        plan = net._plan()
+        if keep['bn'] is not None:                # training mode: the batch statistics the forward normalised with
+            bn = keep['bn']
+        else:                                      # eval mode: the running statistics as a fixed affine of the bias-free conv outputs
+            rows = []
+            for ac, _cv, _g, _s in plan:
+                sl = ac._shift_and_log_scale
+                for conv, m in ((sl.conv2d_1, sl.net[1]), (sl.conv2d_2, sl.net[4])):
+                    rows += [m.running_mean - conv.bias.detach(), torch.rsqrt(m.running_var + BN_EPS), m.running_var]
+            bn = torch.cat(rows).view(P, 24).contiguous()
+        ctx.clean, ctx.train = keep['clean'], keep['bn'] is not None
+        ctx.us, ctx.bn, ctx.sdn = keep['u'], bn, keep['sdn']
+        ctx.prm = torch.cat([t.detach().reshape(-1) for t in cparams]).view(P, 301)
+        ctx.winv = torch.from_numpy(np.stack(keep['winv']).reshape(P, 16)).to(dev)
+        ctx.abd = torch.tensor(keep['ab'], **f32)
+        ctx.shapes = [tuple(t.shape) for t in cparams[:12]]
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        L = _lib.lib()
+        us, clean = ctx.us, ctx.clean
+        P = len(us)
+        B, _c, H, W = us[0].shape
+        f32 = dict(dtype=torch.float32, device=us[0].device)
+        gout = gout.contiguous().float()
+        L.pnnp_nf_sample_bwd_part_floats.restype = C.c_int64
+        part = torch.empty(int(L.pnnp_nf_sample_bwd_part_floats(B, H, W)), **f32)
+        work = torch.empty((5, B, 4, H, W), **f32)                      # h1, h2, out3, dy2, dy1
+        dbuf = [torch.empty((B, 4, H, W), **f32), torch.empty((B, 4, H, W), **f32)]
+        gprm = torch.empty((P, 301), **f32); dwinv = torch.empty((P, 16), **f32); dab = torch.zeros(2, **f32)
+        sums = torch.empty(319, **f32)
+        st = _lib.stream()
+        dout = gout
+        for k in range(P - 1, -1, -1):
+            cl = clean if ctx.sdn[k] else None
+            du = dbuf[k & 1]
+            _lib.check(L.pnnp_nf_sample_bwd_pair_f32(_lib.ptr(us[k]), _lib.ptr(cl), _lib.ptr(ctx.abd), _lib.ptr(ctx.winv[k]),
+                                                     _lib.ptr(ctx.prm[k]), _lib.ptr(ctx.bn[k]), int(ctx.train), _lib.ptr(dout), _lib.ptr(du),
+                                                     _lib.ptr(gprm[k]), _lib.ptr(dwinv[k]), _lib.ptr(dab), _lib.ptr(work[0]), _lib.ptr(work[1]),
+                                                     _lib.ptr(work[2]), _lib.ptr(work[3]), _lib.ptr(work[4]), _lib.ptr(sums), _lib.ptr(part),
+                                                     B, H, W, st), 'nf_sample_bwd_pair')
+            dout = du
+        wi_t = ctx.winv.view(P, 4, 4).transpose(1, 2)
+        dw = -torch.matmul(wi_t, torch.matmul(dwinv.view(P, 4, 4), wi_t))
+        cg = [g.view(s) for row in gprm for g, s in zip(torch.split(row, list(_CPARAM_SIZES)), ctx.shapes)]
+        dz = dout if ctx.needs_input_grad[2] else None
+        return (None, None, dz, dw, dab) + tuple(cg)
 
 
 class NoiseFlow(nn.Module):
@@ -423,7 +492,55 @@ class NoiseFlow(nn.Module):
         """noise_flow.py:173-188.  kwargs: clean [B,4,H,W] (CUDA), iso (scalar / 0-dim tensor);
         optional ``z`` injects the prior draw (else N(0,1) from the counter-based generator).
         In TRAINING mode (trainer_LRID.py:34-39 never calls .eval() on the proxy it samples from, :420-427) the BatchNorm layers
-        of every coupling use the statistics of the batch being sampled and move their running buffers, as nn.BatchNorm2d does."""
+        of every coupling use the statistics of the batch being sampled and move their running buffers, as nn.BatchNorm2d does.
+
+        ``differentiable=True`` (default False: the result has no graph behind it) returns the same values, bit for bit, with an
+        autograd graph: ``backward()`` runs the kernels of csrc/nf_sample_bwd.hip and reaches every trainable parameter (the
+        couplings, l / u / log_s of each Conv2d1x1, gain / beta1 / beta2, model.9's cam_param / gain_params) and an injected ``z``
+        that requires grad; ``clean`` gets no gradient.  BatchNorm is differentiated in the mode the module is in: through the batch
+        statistics in training mode, as a fixed affine in eval mode.  The TRUE derivative is meant: the reference's own Conv2d1x1
+        inverse goes through ``.cpu()`` (conv2d1x1.py:66-74) and would cut the graph there.  This is what lets the distribution
+        losses (``losses.CDFLoss`` / ``KLD``) fit the proxy: ``trainer.NoiseFlowFitStep.ddl_step``."""
+        if not kwargs.get('differentiable', False):
+            return self._sample_run(kwargs)
+        if any(kwargs.get(k) is not None for k in ('_clean_div', '_mix')):
+            raise PnnpError('NoiseFlow.sample: the fused preprocess (sample_mixed) is not differentiable')
+        clean = kwargs['clean'] if 'clean' in kwargs else kwargs['noise']
+        _lib.require_cuda(clean)
+        plan, wstack, ab = self._sample_algebra(float(kwargs['iso']), clean.device)
+        cparams = [t for ac, _cv, _g, _s in plan for t in _coupling_params(ac)]
+        kw = {k: v for k, v in kwargs.items() if k not in ('z', 'differentiable')}
+        return _SampleChain.apply(self, kw, kwargs.get('z'), wstack, ab, *cparams)
+
+    def _sample_algebra(self, iso, dev):
+        """The 4x4 / scalar algebra of the reversed chain as torch expressions of the parameters, as _loss_train builds it, so that
+        autograd finishes the chain rule: wstack [P,4,4] = P L U per pair of the reversed chain (divided by the GainISO scalar on the
+        pair that multiplies by it) and ab = (beta1 / gain, beta2) of the signal-dependent scale."""
+        plan = self._plan()
+        P = len(plan)
+        mask = torch.tril(torch.ones(4, 4, device=dev), -1); eye = torch.eye(4, device=dev)
+        cvs = [e[1] for e in plan]
+        ls = torch.stack([cv.l for cv in cvs]) * mask + eye
+        log_s = torch.stack([cv.log_s for cv in cvs])
+        us = torch.stack([cv.u for cv in cvs]) * mask.t() + torch.diag_embed(torch.stack([cv.sign_s for cv in cvs]) * torch.exp(log_s))
+        wstack = torch.matmul(torch.stack([cv.p for cv in cvs]), torch.matmul(ls, us))
+        ab = torch.zeros(2, device=dev)
+        for k, (_ac, _cv, g_after, s_after) in enumerate(plan):
+            if g_after is not None:                                      # gain.py:79-86: x * scale after Winv, i.e. W / scale
+                gs = torch.exp(_interp_t(g_after.cam_param, iso) * g_after.gain_params) * iso
+                div = torch.ones(P, 1, 1, device=dev).index_put((torch.tensor([k], device=dev),), gs.reshape(1, 1, 1))
+                wstack = wstack / div
+            if s_after is not None:                                      # signal_dependant.py:37-51
+                cam = _interp_t(s_after.cam_param, iso)
+                beta1 = torch.exp(s_after.beta1 * cam[0]); beta2 = torch.exp(s_after.beta2 * cam[1])
+                gain = torch.exp(s_after.gain * cam[2]) * iso
+                ab = torch.stack([beta1 / gain, beta2])
+        return plan, wstack, ab
+
+    def _sample_run(self, kwargs):
+        """sample() proper.  ``_keep`` (a dict, from _SampleChain): every pair's input gets a buffer of its own and is recorded there
+        with the host-side numbers of its step (the inverse matrix, the signal-dependent a / b) and the batch statistics."""
+        keep = kwargs.get('_keep')
         clean = kwargs['clean'] if 'clean' in kwargs else kwargs['noise']
         _lib.require_cuda(clean)
         clean = clean.contiguous().float()
@@ -488,6 +605,10 @@ class NoiseFlow(nn.Module):
                 beta1 = np.exp(host['s_beta1'] * cam[0]); beta2 = np.exp(host['s_beta2'] * cam[1])
                 gain = np.exp(host['s_gain'] * cam[2]) * np.float32(iso)
                 a, b, cl = np.float32(beta1 / gain), np.float32(beta2), clean
+            if keep is not None:
+                keep['u'].append(cur); keep['winv'].append(w); keep['sdn'].append(cl is not None)
+                if cl is not None:
+                    keep['ab'] = (float(a), float(b))
             last = pair_index == n_pairs - 1
             mix = _mix if (last and _mix is not None) else None
             cdiv_t, cdiv_s = (None, 1.0)
@@ -510,7 +631,10 @@ class NoiseFlow(nn.Module):
                                                   C.c_float(1.0), _lib.ptr(cdiv_t), C.c_float(cdiv_s), _lib.ptr(base), _lib.ptr(mul_t),
                                                   C.c_float(mul_s), C.c_float(lo), C.c_float(hi),
                                                   C.c_void_p(flag.data_ptr()) if flag is not None else None, _lib.ptr(bn_dev), _lib.stream()), 'nf_step_mix')
-            cur, nxt = nxt, cur
+            cur, nxt = (nxt, cur) if keep is None else (nxt, torch.empty_like(clean))
+        if keep is not None:
+            keep.setdefault('ab', (0.0, 1.0))
+            keep['bn'], keep['clean'] = (bn_all if train else None), clean
         return cur
 
     # ------------------------------------------------------------------ the trainer's preprocess around sample(), fused

@@ -481,6 +481,12 @@ class NoiseFlowFitStep:
         self.optimizer.zero_grad(set_to_none=True)
         nll, sd_z = self.net.loss(noise=(imgs_lr - hr) / ratio, clean=hr / ratio, iso=float(iso))
         nll.backward()
+        self._average_grads()
+        self.optimizer.step()
+        self.step_count += 1
+        return nll.detach() + torch.log(ratio).mean(), sd_z * ratio.mean()
+
+    def _average_grads(self):
         if self.world > 1:                       # replicas average their gradients (BatchNorm statistics stay per replica,
             import torch.distributed as dist     # as under the reference's nn.DataParallel): ONE all-reduce of the few
             ps = [p for p in self.net.parameters() if p.grad is not None]           # hundred parameters, flattened
@@ -490,9 +496,6 @@ class NoiseFlowFitStep:
             o = 0
             for p in ps:
                 p.grad.copy_(flat[o:o + p.numel()].view_as(p.grad)); o += p.numel()
-        self.optimizer.step()
-        self.step_count += 1
-        return nll.detach() + torch.log(ratio).mean(), sd_z * ratio.mean()
 
     def score(self, hr, iso=1600, per_crop=False, return_tensors=False):
         """The reference's per-epoch score of the proxy (trainer_NF_SID.py:163-173) on the clean crops ``hr`` [B,4,H,W] (CUDA): the
@@ -522,9 +525,8 @@ class NoiseFlowFitStep:
         between the proxy's samples and the real noise of the pair that ``score`` draws: ``make_pair`` at the step's counters and
         ``net.sample(clean=hr/ratio, iso=iso) * ratio`` under ``no_grad``, compared with ``real - hr``.  Returns a 0-dim device tensor
         without synchronising.  ``x``: ascending float32 CUDA points; by default ``losses.get_x(size=1000, mode='uniform')`` mapped
-        affinely onto the real noise's [min, max] with device ops.  The module keeps its mode; nothing is optimised (a backward through
-        ``NoiseFlow.sample`` is not provided: the gradient with respect to the samples is where ``losses`` stops)."""
-        from . import losses
+        affinely onto the real noise's [min, max] with device ops.  The module keeps its mode; nothing is optimised: this scores a
+        proxy.  ``ddl_step`` fits one with the same loss, through ``NoiseFlow.sample(differentiable=True)``."""
         if kind not in ('cdf', 'kld'):
             raise PnnpError(f"NoiseFlowFitStep.ddl: kind = {kind!r}, expected 'cdf' or 'kld'")
         if not hr.is_cuda:
@@ -538,11 +540,43 @@ class NoiseFlowFitStep:
                 sampled = self.net.sample(clean=hr / ratio, iso=float(iso)) * ratio
         finally:
             self.net.train(training)
-        noise = real - hr
+        return self._ddl_of(sampled, real - hr, kind, x)
+
+    @staticmethod
+    def _ddl_of(sampled, noise, kind, x):
+        from . import losses
         if x is None:
             lo, hi = noise.min(), noise.max()
-            x = lo + losses.get_x(size=1000, mode='uniform').to(hr.device) * (hi - lo)
+            x = lo + losses.get_x(size=1000, mode='uniform').to(noise.device) * (hi - lo)
             sorted_ = True                       # ascending by construction: no host read
         else:
             sorted_ = None
         return (losses.CDFLoss if kind == 'cdf' else losses.KLD)(sampled, noise, x, assume_sorted=sorted_)
+
+    def ddl_step(self, hr, iso=1600, kind='cdf', x=None, lr=None):
+        """One fitting step on a distribution loss (the reference's second way of training the proxy, utils/kld_div.py:56-74): with
+        ``net`` in training mode, the pair of ``make_pair`` at the step's counters,
+
+            sampled = net.sample(clean=hr/ratio, iso=iso, differentiable=True) * ratio;  loss = ddl's loss against real - hr
+
+        then ``backward()`` through the sample chain (csrc/nf_sample_bwd.hip), the gradient average over the replicas as in ``step``,
+        Adam, ``step_count += 1``.  Returns the detached 0-dim loss.  ``x``, ``kind`` as for ``ddl``; ``lr`` as for ``step``."""
+        if kind not in ('cdf', 'kld'):
+            raise PnnpError(f"NoiseFlowFitStep.ddl_step: kind = {kind!r}, expected 'cdf' or 'kld'")
+        if not hr.is_cuda:
+            raise PnnpError('NoiseFlowFitStep needs CUDA tensors (no CPU path)')
+        if lr is not None:
+            for g in self.optimizer.param_groups:
+                g['lr'] = lr
+        self.net.train()
+        real, ratio = self.make_pair(hr, iso)
+        if self.clip:
+            hr = hr.clamp(0, 1)                  # :442
+        self.optimizer.zero_grad(set_to_none=True)
+        sampled = self.net.sample(clean=hr / ratio, iso=float(iso), differentiable=True) * ratio
+        loss = self._ddl_of(sampled, real - hr, kind, x)
+        loss.backward()
+        self._average_grads()
+        self.optimizer.step()
+        self.step_count += 1
+        return loss.detach()
