@@ -61,6 +61,39 @@ __device__ __forceinline__ void block_sum_store(const float (&v)[N], float* __re
     for (int i = threadIdx.x; i < N; i += 256) out[i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
 }
 
+// One workgroup's share of a BatchNorm's statistics: hv[k][o] = the (up to) four values a thread produced for channel o, ok[k] = that
+// one exists; n = the workgroup's pixel count.  Writes out[0:4] = sum and out[4:8] = sum of squares ABOUT THE WORKGROUP'S OWN MEAN, in
+// two passes over the registers (two barriers, as many as one block_sum_store).  E[x^2] - mean^2 from float32 sums of x^2 loses
+// (mean/std)^2 float32 roundings: with one pixel it gave var ~ 6e-8 x^2 in place of 0 (rstd off by 1e-3 .. 1e-1), with |mean| = 6 std
+// a variance wrong in the 6th digit.  `red` must not be in use when this is called.
+__device__ __forceinline__ void block_stats_store(const float (&hv)[4][4], const bool (&ok)[4], int n, float* __restrict__ out, float (*red)[4]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v += ok[k] ? hv[k][o] : 0.f;
+        v = wave_sum_lane63(v);
+        if (lane == 63) red[o][wave] = v;
+    }
+    __syncthreads();
+    const float inv = 1.f / (float)n;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const float m = ((red[o][0] + red[o][1]) + (red[o][2] + red[o][3])) * inv;
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float d = hv[k][o] - m;
+            v += ok[k] ? d * d : 0.f;
+        }
+        v = wave_sum_lane63(v);
+        if (lane == 63) red[4 + o][wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) out[threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
 struct PairIn {
     const float* x;          // [B][4][H][W]
     const float* clean;      // [B][4][H][W] or null
@@ -83,7 +116,7 @@ __device__ __forceinline__ void load_xp(const PairIn& p, const float* xb, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------- forward
-// pass 1: h1 = conv2d_1(v[0:2]) and the per-workgroup sums of h1, h1^2
+// pass 1: h1 = conv2d_1(v[0:2]) and the per-workgroup statistics of h1 (block_stats_store)
 __global__ void __launch_bounds__(256)
 nf_tr_conv1_kernel(PairIn p, float* __restrict__ h1, float* __restrict__ part) {
     __shared__ float vs[2][HS][HS + 1];
@@ -104,10 +137,13 @@ nf_tr_conv1_kernel(PairIn p, float* __restrict__ h1, float* __restrict__ part) {
         vs[0][r][q] = v0; vs[1][r][q] = v1;
     }
     __syncthreads();
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < TS * TS; i += 256) {
-        const int r = i / TS, q = i % TS, gy = ty0 + r, gx = tx0 + q;
-        if (gy >= H || gx >= W) continue;
+    static_assert(TS * TS == 4 * 256, "four pixels per thread");
+    float hv[4][4];
+    bool ok[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + 256 * k, r = i / TS, q = i % TS, gy = ty0 + r, gx = tx0 + q;
+        ok[k] = gy < H && gx < W;
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             float s = 0.f;                   // bias-free: see the note on h1/h2 at the top of the file
@@ -115,29 +151,50 @@ nf_tr_conv1_kernel(PairIn p, float* __restrict__ h1, float* __restrict__ part) {
             for (int c = 0; c < 2; ++c)
 #pragma unroll
                 for (int t = 0; t < 9; ++t) s += p.prm[P_W1 + (o * 2 + c) * 9 + t] * vs[c][r + t / 3][q + t % 3];
-            h1[((int64_t)b * 4 + o) * plane + (int64_t)gy * W + gx] = s;
-            acc[o] += s; acc[4 + o] += s * s;
+            if (ok[k]) h1[((int64_t)b * 4 + o) * plane + (int64_t)gy * W + gx] = s;
+            hv[k][o] = s;
         }
     }
-    block_sum_store<8>(acc, part + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8, red);
+    block_stats_store(hv, ok, min(TS, H - ty0) * min(TS, W - tx0),
+                      part + (((int64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8, red);
 }
 
-// statistics of one BatchNorm: part [rows][8] (sum[4], sumsq[4]) -> bn[0:12] = mean, rstd, biased var
+// statistics of one BatchNorm: part [rows][8] (sum[4], sum of squares about the row's own mean[4]) -> bn[0:12] = mean, rstd, biased var.
+// The rows are merged as  N var = sum_r M2_r + sum_r n_r (mean_r - mean)^2,  the second sum taken about the first row's mean c in
+// double:  sum_r n_r (mean_r - c)^2 - N (mean - c)^2.   n_r follows from the row index: a 32x32 tile of an H x W image clipped at its
+// edges (the tiled pass), or, with H == 0, 1024 consecutive pixels of npix (the pointwise pass).
 __global__ void __launch_bounds__(1024)
-nf_tr_bnstat_kernel(const float* __restrict__ part, int rows, double inv_n, float* __restrict__ bn) {
+nf_tr_bnstat_kernel(const float* __restrict__ part, int rows, double inv_n, float* __restrict__ bn, int H, int W, int64_t npix) {
     __shared__ double red[1024];
+    __shared__ double red2[1024];
     const int col = threadIdx.x & 7;
-    double s = 0.0;
-    for (int r = threadIdx.x >> 3; r < rows; r += 128) s += (double)part[(int64_t)r * 8 + col];
-    red[threadIdx.x] = s;
+    const int gx = H ? (W + TS - 1) / TS : 1, gy = H ? (H + TS - 1) / TS : 1;
+    const bool full = H && H % TS == 0 && W % TS == 0;      // (the common case: no division per row)
+    auto count = [&](int r) {
+        if (full) return TS * TS;
+        if (!H) return r == rows - 1 ? (int)(npix - (int64_t)r * 1024) : 1024;
+        return min(TS, H - TS * ((r / gx) % gy)) * min(TS, W - TS * (r % gx));
+    };
+    const double c = col < 4 ? (double)part[col] / (double)count(0) : 0.0;
+    double s = 0.0, s2 = 0.0;
+    for (int r = threadIdx.x >> 3; r < rows; r += 128) {
+        const double v = (double)part[(int64_t)r * 8 + col];
+        s += v;
+        if (col < 4) {
+            const int n = count(r);
+            const double d = (n == 1024 ? v * (1.0 / 1024.0) : v / (double)n) - c;
+            s2 += (double)n * d * d;
+        }
+    }
+    red[threadIdx.x] = s; red2[threadIdx.x] = s2;
     __syncthreads();
     for (int k = 512; k >= 8; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        if (threadIdx.x < k) { red[threadIdx.x] += red[threadIdx.x + k]; red2[threadIdx.x] += red2[threadIdx.x + k]; }
         __syncthreads();
     }
     if (threadIdx.x < 4) {
         const double m = red[threadIdx.x] * inv_n;
-        double var = red[4 + threadIdx.x] * inv_n - m * m;
+        double var = (red[4 + threadIdx.x] + red2[threadIdx.x]) * inv_n - (m - c) * (m - c);
         if (var < 0.0) var = 0.0;
         bn[threadIdx.x] = (float)m;
         bn[4 + threadIdx.x] = (float)(1.0 / sqrt(var + (double)BN_EPS));
@@ -145,15 +202,20 @@ nf_tr_bnstat_kernel(const float* __restrict__ part, int rows, double inv_n, floa
     }
 }
 
-// pass 2 (pointwise over B*H*W pixels, 1024 per workgroup): h2 = conv2d_2(relu(BN1(h1))) and the sums of h2, h2^2
+// pass 2 (pointwise over B*H*W pixels, 1024 per workgroup): h2 = conv2d_2(relu(BN1(h1))) and the per-workgroup statistics of h2
 __global__ void __launch_bounds__(256)
 nf_tr_conv2_kernel(const float* __restrict__ h1, const float* __restrict__ prm, const float* __restrict__ bn, float* __restrict__ h2,
                    float* __restrict__ part, int64_t plane, int64_t npix) {
     __shared__ float red[8][4];
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float hv[4][4];
+    bool ok[4];
+#pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int64_t g = (int64_t)blockIdx.x * 1024 + k * 256 + threadIdx.x;
-        if (g >= npix) break;
+        ok[k] = g < npix;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) hv[k][o] = 0.f;
+        if (!ok[k]) continue;
         const int64_t b = g / plane, pix = g - b * plane, base = b * 4 * plane + pix;
         float a1[4];
 #pragma unroll
@@ -165,10 +227,11 @@ nf_tr_conv2_kernel(const float* __restrict__ h1, const float* __restrict__ prm, 
 #pragma unroll
             for (int c = 0; c < 4; ++c) s += prm[P_W2 + o * 4 + c] * a1[c];
             h2[base + o * plane] = s;
-            acc[o] += s; acc[4 + o] += s * s;
+            hv[k][o] = s;
         }
     }
-    block_sum_store<8>(acc, part + (int64_t)blockIdx.x * 8, red);
+    const int64_t left = npix - (int64_t)blockIdx.x * 1024;
+    block_stats_store(hv, ok, (int)(left < 1024 ? left : 1024), part + (int64_t)blockIdx.x * 8, red);
 }
 
 // a2 = relu(BN2(h2)) on tile + halo 1 (zero outside the image: the ConstantPad3d ring)
@@ -497,9 +560,9 @@ int pnnp_nf_train_fwd_pair_f32(const float* x, const float* clean, const float* 
     const int64_t plane = (int64_t)H * W, npix = (int64_t)B * plane;
     const double inv_n = 1.0 / (double)npix;
     hipLaunchKernelGGL(nf_tr_conv1_kernel, grid, dim3(256), 0, st, p, h1, part);
-    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, tiles, inv_n, bn);
+    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, tiles, inv_n, bn, H, W, npix);
     hipLaunchKernelGGL(nf_tr_conv2_kernel, dim3(pb), dim3(256), 0, st, h1, prm, bn, h2, part, plane, npix);
-    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, pb, inv_n, bn + 12);
+    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, pb, inv_n, bn + 12, 0, 0, npix);
     hipLaunchKernelGGL(nf_tr_couple_kernel, grid, dim3(256), 0, st, p, h2, z, out3, ldpart);
     return pnnp_launch_status();
 }
@@ -518,9 +581,9 @@ int pnnp_nf_train_stats_f32(const float* u, const float* ident, const float* prm
     const int64_t plane = (int64_t)H * W, npix = (int64_t)B * plane;
     const double inv_n = 1.0 / (double)npix;
     hipLaunchKernelGGL(nf_tr_conv1_kernel, grid, dim3(256), 0, st, p, h1, part);
-    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, tiles, inv_n, bn);
+    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, tiles, inv_n, bn, H, W, npix);
     hipLaunchKernelGGL(nf_tr_conv2_kernel, dim3(pb), dim3(256), 0, st, h1, prm, bn, h2, part, plane, npix);
-    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, pb, inv_n, bn + 12);
+    hipLaunchKernelGGL(nf_tr_bnstat_kernel, dim3(1), dim3(1024), 0, st, part, pb, inv_n, bn + 12, 0, 0, npix);
     return pnnp_launch_status();
 }
 

@@ -14,7 +14,8 @@ ARCH = 'sdn|unc|unc|unc|unc|giso|unc|unc|unc|unc'
 def _close_chain(got, ref):
     """Eight chained couplings (x1 = (z1 - shift) * exp(-s*tanh(.))) and 4x4 inverses in fp32: device
     expf/tanhf differ from the CPU's by ulps and the (z1 - shift) cancellation amplifies that at a few
-    pixels.  Bar: >= 99.9 % of elements within rtol 2e-4 (+2e-4 of the output scale), all within 5 %."""
+    pixels.  Bar: >= 99.9 % of elements within rtol 2e-4 (+2e-4 of the output scale), all within 5 %.
+    What this bar cannot see at few pixels, tests/test_gpu_nf_pairs.py checks one pair at a time, per pixel against float64."""
     scale = np.abs(ref).max()
     err = np.abs(got - ref)
     tight = err <= 2e-4 * np.abs(ref) + 2e-4 * scale
