@@ -714,6 +714,35 @@ int pnnp_cdf_loss_f32(const float* output, int64_t n_output, const float* gt, in
 int pnnp_kld_loss_f32(const float* output, int64_t n_output, const float* gt, int64_t n_gt, const float* x, int k, void* ws,
                       float* cdf, int* brackets, float* loss, float* dcdf, void* stream);
 
+/* ---------------------------------------------------------------- QuantileLoss (csrc/quantile.hip; utils/kld_div.py:49-53)
+ * torch.quantile(..., dim=-1, interpolation='linear') of `rows` rows of n float32 samples at k probabilities q, the L1 loss between the
+ * quantiles of two operands and the gradient with respect to the samples, by an exact multi-rank select: no sort.  Per probability, in float32
+ * on the device:  pos = q * float(n - 1);  lo = floor(pos);  hi = ceil(pos);  w = pos - floor(pos)  (lo, hi clamped into [0, n - 1]);
+ * value = w < 0.5 ? a + w * (b - a) : b - (b - a) * (1 - w)  with a = s[lo], b = s[hi] of the row sorted ascending, unfused.  The order
+ * statistics are exact for any finite or infinite input (-0.0 orders as +0.0); among equal samples the LOWEST index holds an order statistic
+ * (and receives its gradient).  q need not be ascending and may repeat; it is not validated.  NaN samples are not supported (no index leaves
+ * [0, n)).  float32 only; 1 <= n < 2^31; 1 <= k <= PNNP_QUANTILE_MAX_K; rows >= 1; anything else is PNNP_E_UNSUPPORTED before a launch.
+ * Three passes over the samples whatever they hold (range, census, gather); no synchronisation, nothing allocated; integer atomics and
+ * fixed-order float64 sums only: bitwise reproducible.  Arrays may start at any element; rows are contiguous ([rows][n]).
+ *   pnnp_quantile_ws_bytes   the workspace of a call on operands of n_a and n_b samples per row (n_b = 0: one operand); ws is 16-byte aligned
+ *                            and need not be zeroed.  It holds 8 bytes per sample (the worst case of the gather: all samples equal).
+ *   pnnp_quantile_f32        values [k][rows] (the layout torch.quantile returns); arg [2][rows][k] int32 = the element of its row that holds
+ *                            s[lo], then s[hi]; w [k].
+ *   pnnp_quantile_bwd_f32    grad [rows][n] (zeroed here) of sum g[k][r] value[k][r]: g (1 - w) to arg lo, g w to arg hi (g times scale[0] when
+ *                            scale, a device pointer, is given); contributions that meet on an element are summed in float64 in a fixed
+ *                            order and rounded once.
+ *   pnnp_quantile_loss_f32   QuantileLoss: loss [1] = mean over k, rows of |value_output - value_gt|; values [2][k][rows], arg [2][2][rows][k],
+ *                            w [2][k] (output, gt: their n may differ), dq [2][k][rows] = dL/dvalue = +-sign(difference) / (k rows), 0 at 0:
+ *                            what pnnp_quantile_bwd_f32 takes as g, with the upstream scalar as scale.
+ * These entries were added under ABI version 9 (entries only): a binding finds an older library by the missing symbol. */
+#define PNNP_QUANTILE_MAX_K 1024
+int64_t pnnp_quantile_ws_bytes(int rows, int64_t n_a, int64_t n_b, int k);
+int pnnp_quantile_f32(const float* data, int rows, int64_t n, const float* q, int k, void* ws, float* values, int* arg, float* w, void* stream);
+int pnnp_quantile_bwd_f32(int rows, int64_t n, int k, const int* arg, const float* w, const float* g, const float* scale /*[device], may be NULL*/,
+                          float* grad, void* stream);
+int pnnp_quantile_loss_f32(const float* output, int64_t n_output, const float* gt, int64_t n_gt, int rows, const float* q, int k, void* ws,
+                           float* values, int* arg, float* w, float* loss, float* dq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

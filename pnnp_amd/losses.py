@@ -1,6 +1,7 @@
-"""Differentiable distribution losses on the device (reference: utils/kld_div.py:21-98; csrc/ddl.hip): the linearly interpolated
-empirical CDF of a sample set (``CDFPPF.get_cdf``), ``CDFLoss``, ``KLD``, ``cdf2pdf`` and the evaluation points ``get_x``, under the
-reference's names and signatures.  Everything but ``get_x`` takes float32 CUDA tensors and is a ``torch.autograd.Function``:
+"""Differentiable distribution losses on the device (reference: utils/kld_div.py:21-98; csrc/ddl.hip, csrc/quantile.hip): the linearly
+interpolated empirical CDF of a sample set (``CDFPPF.get_cdf``), ``CDFLoss``, ``KLD``, ``cdf2pdf``, ``QuantileLoss`` (with ``quantile``,
+the ``torch.quantile(..., dim=-1, interpolation='linear')`` it is built on) and the evaluation points ``get_x``, under the reference's
+names and signatures.  Everything but ``get_x`` takes float32 CUDA tensors and is a ``torch.autograd.Function``:
 ``loss.backward()`` reaches whichever of ``output`` / ``gt`` requires grad.  The gradient stops at the samples and at the points
 ``x`` (the reference would also differentiate with respect to ``x``; nothing in it does).
 
@@ -13,7 +14,13 @@ are never modified.  There is no CPU fallback: CPU tensors, another dtype or siz
 
 The kernels take ascending points.  ``assume_sorted=None`` (the default) checks that with one host read and, if ``x`` is not
 ascending, sorts it with ``torch.sort`` and un-permutes the result (K elements of plumbing); ``assume_sorted=True`` skips the check
-and the synchronisation it costs (``NoiseFlowFitStep.ddl`` does, its default points are ascending by construction)."""
+and the synchronisation it costs (``NoiseFlowFitStep.ddl`` does, its default points are ascending by construction).
+
+``quantile`` / ``QuantileLoss`` compare in the value domain.  Where ``torch.quantile`` sorts every row, the kernels select the 2K order
+statistics a row needs exactly in three streaming passes (range, a 2^15-bin census, a gather of the bins that hold a wanted rank) and a
+finish per gathered bin.  Ranks and weights follow torch's float32 rule (``pos = q * float32(N - 1)``); the probabilities need not be
+ascending, may repeat and are not read on the host.  The same tie rule, NaN and no-fallback terms as above apply, with
+1 <= N < 2^31 per row and 1 <= K <= QUANTILE_MAX_K; rows are the flattened leading dimensions."""
 import ctypes as C
 
 import torch
@@ -21,6 +28,7 @@ import torch
 from . import _lib
 
 MAX_K = 4096                     # PNNP_DDL_MAX_K
+QUANTILE_MAX_K = 1024            # PNNP_QUANTILE_MAX_K
 
 
 def _ddl_lib():
@@ -195,6 +203,150 @@ def KLD(output, gt, x_pdf, assume_sorted=None):
     factor = torch.max(q.sum(), p.sum()).detach()
     q, p = q / factor, p / factor
     return torch.sum(p * (torch.log(p) - torch.log(q)))
+
+
+def _quantile_lib():
+    L = _lib.lib()
+    if not hasattr(L, 'pnnp_quantile_loss_f32'):
+        raise _lib.PnnpError('libpnnp_hip.so has no pnnp_quantile_* entries: it was built before they were added (rebuild with tools/build.py)')
+    if L.pnnp_quantile_ws_bytes.restype is not C.c_int64:
+        L.pnnp_quantile_ws_bytes.restype = C.c_int64
+        L.pnnp_quantile_ws_bytes.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int]
+    return L
+
+
+def _rows(t, what):
+    """The samples as contiguous detached float32 rows [R, N] over the last dimension (a copy only if it has to be)."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.PnnpError(f'{what}: expected a tensor, got {type(t).__name__}')
+    _lib.require_cuda(t)
+    if t.dtype != torch.float32:
+        raise _lib.PnnpError(f'{what}: the distribution losses take float32 tensors, got {t.dtype}')
+    if t.dim() < 1:
+        raise _lib.PnnpError(f'{what}: a 0-dim tensor has no last dimension')
+    n = t.shape[-1]
+    if not 1 <= n < 2 ** 31:
+        raise _lib.PnnpError(f'{what}: {n} samples per row, the kernels take 1 <= N < 2^31')
+    rows = t.numel() // n
+    if not 1 <= rows <= 32767:
+        raise _lib.PnnpError(f'{what}: {rows} rows, the kernels take 1 <= rows <= 32767')
+    return t.detach().reshape(rows, n).contiguous()
+
+
+def _probabilities(q, what, device):
+    if not isinstance(q, torch.Tensor):
+        raise _lib.PnnpError(f'{what}: expected a tensor of probabilities, got {type(q).__name__}')
+    _lib.require_cuda(q)
+    if q.dtype != torch.float32:
+        raise _lib.PnnpError(f'{what}: the probabilities must be float32, got {q.dtype}')
+    if q.dim() > 1:
+        raise _lib.PnnpError(f'{what}: the probabilities must be 0-dim or 1-D, got {q.dim()} dimensions')
+    k = q.numel()
+    if not 1 <= k <= QUANTILE_MAX_K:
+        raise _lib.PnnpError(f'{what}: {k} probabilities, the kernels take 1 <= K <= {QUANTILE_MAX_K}')
+    if q.device != device:
+        raise _lib.PnnpError(f'{what}: the probabilities and the samples are on different devices')
+    return q.detach().reshape(-1).contiguous()
+
+
+def _quantile_workspace(L, rows, n_a, n_b, k, device):
+    nbytes = int(L.pnnp_quantile_ws_bytes(rows, n_a, n_b, k))
+    if nbytes < 0:
+        _lib.check(nbytes, 'pnnp_quantile_ws_bytes')
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _quantile_backward(rows, n, arg, w, g, scale):
+    """grad [R, N] of sum g[k, r] value[k, r] (g times the device scalar ``scale`` if given) with respect to the rows"""
+    grad = torch.empty(rows, n, dtype=torch.float32, device=g.device)
+    _lib.check(_quantile_lib().pnnp_quantile_bwd_f32(rows, C.c_int64(n), w.numel(), _lib.ptr(arg), _lib.ptr(w), _lib.ptr(g), _lib.ptr(scale),
+                                                     _lib.ptr(grad), _lib.stream()), 'pnnp_quantile_bwd_f32')
+    return grad
+
+
+def quantile_with_state(data, q):
+    """``torch.quantile(data, q, dim=-1, interpolation='linear')`` of float32 CUDA ``data`` as [K, R] (R: the flattened leading dimensions)
+    and the kernel's state: arg int32 [2, R, K] (the element of its row that holds s[lo], then s[hi]: the lowest index among equal
+    values) and the weights w [K].  No autograd."""
+    rows = _rows(data, 'quantile')
+    q = _probabilities(q, 'quantile', rows.device)
+    L = _quantile_lib()
+    r, n, k = rows.shape[0], rows.shape[1], q.numel()
+    values = torch.empty(k, r, dtype=torch.float32, device=rows.device)
+    arg = torch.empty(2, r, k, dtype=torch.int32, device=rows.device)
+    w = torch.empty(k, dtype=torch.float32, device=rows.device)
+    ws = _quantile_workspace(L, r, n, 0, k, rows.device)
+    _lib.check(L.pnnp_quantile_f32(_lib.ptr(rows), r, C.c_int64(n), _lib.ptr(q), k, _lib.ptr(ws), _lib.ptr(values), _lib.ptr(arg), _lib.ptr(w),
+                                   _lib.stream()), 'pnnp_quantile_f32')
+    return values, arg, w
+
+
+class _Quantile(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, data, q):
+        values, arg, w = quantile_with_state(data, q)
+        ctx.save_for_backward(arg, w)
+        ctx.shape = data.shape
+        out_shape = (() if q.dim() == 0 else (q.numel(),)) + tuple(data.shape[:-1])
+        return values.view(out_shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        arg, w = ctx.saved_tensors
+        rows, n = arg.shape[1], ctx.shape[-1]
+        g = g.to(torch.float32).reshape(w.numel(), rows).contiguous()
+        return _quantile_backward(rows, n, arg, w, g, None).view(ctx.shape), None
+
+
+def quantile(data, q):
+    """``torch.quantile(data, q, dim=-1, keepdim=False, interpolation='linear')`` for float32 CUDA tensors: [K, *leading] (a 0-dim ``q``
+    gives [*leading]).  Differentiable with respect to ``data`` only."""
+    return _Quantile.apply(data, q)
+
+
+class _QuantileLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, gt, q):
+        o, g = _rows(output, 'QuantileLoss: output'), _rows(gt, 'QuantileLoss: gt')
+        if o.device != g.device:
+            raise _lib.PnnpError('QuantileLoss: output and gt are on different devices')
+        q = _probabilities(q, 'QuantileLoss', o.device)
+        if o.shape[0] != g.shape[0]:
+            raise _lib.PnnpError(f'QuantileLoss: output has {o.shape[0]} rows and gt {g.shape[0]}')
+        L = _quantile_lib()
+        r, k, dev = o.shape[0], q.numel(), o.device
+        values = torch.empty(2, k, r, dtype=torch.float32, device=dev)
+        dq = torch.empty(2, k, r, dtype=torch.float32, device=dev)
+        arg = torch.empty(2, 2, r, k, dtype=torch.int32, device=dev)
+        w = torch.empty(2, k, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _quantile_workspace(L, r, o.shape[1], g.shape[1], k, dev)
+        _lib.check(L.pnnp_quantile_loss_f32(_lib.ptr(o), C.c_int64(o.shape[1]), _lib.ptr(g), C.c_int64(g.shape[1]), r, _lib.ptr(q), k, _lib.ptr(ws),
+                                            _lib.ptr(values), _lib.ptr(arg), _lib.ptr(w), _lib.ptr(loss), _lib.ptr(dq), _lib.stream()),
+                   'pnnp_quantile_loss_f32')
+        ctx.save_for_backward(arg, w, dq)
+        ctx.shapes = (output.shape, gt.shape)
+        ctx.ns = (o.shape[1], g.shape[1])
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gup):
+        arg, w, dq = ctx.saved_tensors
+        scale = gup.to(torch.float32).reshape(1).contiguous()
+        grads = [None, None]
+        for i in range(2):
+            if ctx.needs_input_grad[i]:
+                grads[i] = _quantile_backward(arg.shape[2], ctx.ns[i], arg[i], w[i], dq[i], scale).view(ctx.shapes[i])
+        return grads[0], grads[1], None
+
+
+def QuantileLoss(output, gt, x_quant):
+    """utils/kld_div.py:49-53: mean |quantile(output, x_quant, dim=-1) - quantile(gt, x_quant, dim=-1)|, a 0-dim device tensor.  1-D
+    operands may differ in length; operands with leading dimensions are compared row by row (the same number of rows) and the mean
+    runs over all K x R differences.  One fused call: both operands, the mean and dL/dquantile."""
+    return _QuantileLoss.apply(output, gt, x_quant)
 
 
 def get_x(sigma=4, size=1000, mode='uniform', random=True):

@@ -529,18 +529,39 @@ class NoiseFlowFitStep:
         proxy.  ``ddl_step`` fits one with the same loss, through ``NoiseFlow.sample(differentiable=True)``."""
         if kind not in ('cdf', 'kld'):
             raise PnnpError(f"NoiseFlowFitStep.ddl: kind = {kind!r}, expected 'cdf' or 'kld'")
+        return self._pair_loss(hr, iso, lambda sampled, noise: self._ddl_of(sampled, noise, kind, x), fit=False)
+
+    def _pair_loss(self, hr, iso, loss_of, fit, lr=None):
+        """The body that ``ddl`` / ``qloss`` (``fit=False``) and ``ddl_step`` / ``qloss_step`` (``fit=True``) share: the pair of
+        ``make_pair`` at the step's counters, the proxy's samples, ``loss_of(sampled, real - hr)``.  Scoring samples under ``no_grad``
+        and restores the module's mode; fitting samples differentiably in training mode, then ``backward()``, the replica average,
+        Adam and ``step_count += 1``, and returns the detached loss."""
         if not hr.is_cuda:
             raise PnnpError('NoiseFlowFitStep needs CUDA tensors (no CPU path)')
+        if fit:
+            if lr is not None:
+                for g in self.optimizer.param_groups:
+                    g['lr'] = lr
+            self.net.train()
         training = self.net.training
         real, ratio = self.make_pair(hr, iso)
         if self.clip:
             hr = hr.clamp(0, 1)                  # :442
-        try:
-            with torch.no_grad():
-                sampled = self.net.sample(clean=hr / ratio, iso=float(iso)) * ratio
-        finally:
-            self.net.train(training)
-        return self._ddl_of(sampled, real - hr, kind, x)
+        if not fit:
+            try:
+                with torch.no_grad():
+                    sampled = self.net.sample(clean=hr / ratio, iso=float(iso)) * ratio
+            finally:
+                self.net.train(training)
+            return loss_of(sampled, real - hr)
+        self.optimizer.zero_grad(set_to_none=True)
+        sampled = self.net.sample(clean=hr / ratio, iso=float(iso), differentiable=True) * ratio
+        loss = loss_of(sampled, real - hr)
+        loss.backward()
+        self._average_grads()
+        self.optimizer.step()
+        self.step_count += 1
+        return loss.detach()
 
     @staticmethod
     def _ddl_of(sampled, noise, kind, x):
@@ -563,20 +584,24 @@ class NoiseFlowFitStep:
         Adam, ``step_count += 1``.  Returns the detached 0-dim loss.  ``x``, ``kind`` as for ``ddl``; ``lr`` as for ``step``."""
         if kind not in ('cdf', 'kld'):
             raise PnnpError(f"NoiseFlowFitStep.ddl_step: kind = {kind!r}, expected 'cdf' or 'kld'")
-        if not hr.is_cuda:
-            raise PnnpError('NoiseFlowFitStep needs CUDA tensors (no CPU path)')
-        if lr is not None:
-            for g in self.optimizer.param_groups:
-                g['lr'] = lr
-        self.net.train()
-        real, ratio = self.make_pair(hr, iso)
-        if self.clip:
-            hr = hr.clamp(0, 1)                  # :442
-        self.optimizer.zero_grad(set_to_none=True)
-        sampled = self.net.sample(clean=hr / ratio, iso=float(iso), differentiable=True) * ratio
-        loss = self._ddl_of(sampled, real - hr, kind, x)
-        loss.backward()
-        self._average_grads()
-        self.optimizer.step()
-        self.step_count += 1
-        return loss.detach()
+        return self._pair_loss(hr, iso, lambda sampled, noise: self._ddl_of(sampled, noise, kind, x), fit=True, lr=lr)
+
+    @staticmethod
+    def _qloss_of(sampled, noise, q, per_crop):
+        from . import losses
+        if q is None:
+            q = losses.get_x(size=1000, mode='uniform').to(noise.device)
+        shape = (noise.shape[0], -1) if per_crop else (-1,)
+        return losses.QuantileLoss(sampled.reshape(shape), noise.reshape(shape), q)
+
+    def qloss(self, hr, iso=1600, q=None, per_crop=False):
+        """``losses.QuantileLoss`` (utils/kld_div.py:49-53: the L1 mean between quantiles, a comparison in the value domain) between the
+        proxy's samples and the real noise, drawn exactly as for ``ddl``: a 0-dim device tensor, no synchronisation, nothing optimised,
+        the module keeps its mode.  ``q``: float32 CUDA probabilities, at most ``losses.QUANTILE_MAX_K``; by default
+        ``losses.get_x(size=1000, mode='uniform')``.  ``per_crop=True`` compares crop by crop on [B, 4*H*W] and averages over all K x B
+        differences (the crops of a batch have different K and ratio, which a pooled quantile mixes); otherwise the batch is pooled."""
+        return self._pair_loss(hr, iso, lambda sampled, noise: self._qloss_of(sampled, noise, q, per_crop), fit=False)
+
+    def qloss_step(self, hr, iso=1600, q=None, per_crop=False, lr=None):
+        """One fitting step on ``QuantileLoss``: ``ddl_step`` with the loss of ``qloss``.  Returns the detached 0-dim loss."""
+        return self._pair_loss(hr, iso, lambda sampled, noise: self._qloss_of(sampled, noise, q, per_crop), fit=True, lr=lr)
