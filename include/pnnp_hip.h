@@ -595,6 +595,28 @@ int pnnp_nf_sample_bwd_pair_f32(const float* u, const float* clean /*or null*/, 
 int pnnp_sna_f32(const float* gt, float* dn, float* dy, int C, int H, int W, const float* aug_wb4, float K, float wp, float bl,
                  float ratio, int black_lr, int ori, uint64_t seed, uint64_t offset, uint32_t crop, void* stream);
 
+/* The paired-data branch of Trainer.preprocess (trainer_SID.py:430-447,481-485; trainer_LRID.py:367-397,436-439: datasets Mix_Dataset,
+ * IMX686_Mix_Dataset, IMX686_SFRN_Raw_Dataset) in ONE launch over a batch: per crop i the digital gain on lr, SNA_torch on hr, the two
+ * adds and the trainer's clamp.  lr, hr, lr_out, hr_out: f32 [B][4][H][W] (device); an output may alias ITS OWN input (every element is
+ * read and written by one thread).  rows: f32 [B][PNNP_SNA_NPARAM] (device), one row per crop; nothing is read back.  Per element of
+ * plane c, in float32, every operation rounded on its own:
+ *   l = ori ? lr : lr*ratio
+ *   if active:  g = hr*(wp-bl)/ratio;  y = g*aug[c];  n = Poisson(y/K)*K;  if black_lr: y -= g;  y = y*ratio/(wp-bl);  n = n/(wp-bl);
+ *               if !ori: n *= ratio;   l += n;   if add_dy: hr += y
+ *   PNNP_SNA_CLIP_MAX1: l = min(l,1), hr = clamp(hr,0,1);  PNNP_SNA_CLIP_MIN0 (with MAX1): l = max(l,0)
+ * The Poisson draw of element t of global crop crop_base+i is pnnp_sna_f32's (same Philox block, same sampler): a batched call is
+ * bit-equal to that entry followed by the adds, and independent of batch size, grid and rank.  An active row needs K > 0 and
+ * ratio > 0 (the caller's duty: rows live on the device).  PNNP_E_INVALID: null pointers, 4*H*W >= 2^32, B >= 2^24. */
+enum {
+    PNNP_SNA_AUG0 = 0, PNNP_SNA_AUG1, PNNP_SNA_AUG2, PNNP_SNA_AUG3, PNNP_SNA_K, PNNP_SNA_WP, PNNP_SNA_BL, PNNP_SNA_RATIO,
+    PNNP_SNA_ACTIVE, PNNP_SNA_BLACK_LR, PNNP_SNA_ADD_DY, PNNP_SNA_NPARAM = 12
+};
+#define PNNP_SNA_ORI 0x1u        /* dst.ori: lr is not multiplied by the ratio, nor is the noise */
+#define PNNP_SNA_CLIP_MAX1 0x2u  /* dst.clip set: lr <= 1, hr in [0,1] */
+#define PNNP_SNA_CLIP_MIN0 0x4u  /* dst.clip other than HALF_CLIP: lr >= 0 as well */
+int pnnp_sna_batch_f32(const float* lr, const float* hr, float* lr_out, float* hr_out, int B, int H, int W, const float* rows,
+                       unsigned flags, uint64_t seed, uint64_t offset, uint32_t crop_base, void* stream);
+
 /* HighBitRecovery.map (data_process/process.py:718-751): pixels whose rounded value x lies in [low, high) are re-drawn
  * inside their quantisation bin, d' = ppf(cdf[x-low] + u*range[x-low]) + (d - x); d = data*in_mul; the result is
  * divided by out_div (norm=True) or, if out_div == 0, shifted by out_add (norm=False).  cdf/range: float64 device LUTs of

@@ -451,6 +451,85 @@ sna_kernel(const float* __restrict__ gt, float* __restrict__ dn, float* __restri
     }
 }
 
+// The paired-data branch of Trainer.preprocess (trainer_SID.py:430-447,481-485; trainer_LRID.py:367-397) over a whole batch: the digital
+// gain on lr, sna_kernel's arithmetic on hr, `lr += dn`, `hr += dy` and the trainer's clamp in one pass -- 16 B per element.  Per element
+// the float32 operations of sna_kernel followed by torch's mul / add / clamp, in their order, each rounded on its own; the Philox block
+// and the sampler are sna_kernel's, so the draw is that entry's bit for bit.
+// Layout: blockIdx.y walks the crops, so a crop's row of the parameter table is read through the scalar unit and its flags (active,
+// black_lr, add_dy) branch wave-uniformly; a thread owns 4 consecutive elements of the crop's [4][H][W] block (a crop holds 4*H*W
+// elements, so quads never straddle crops, and a crop starts 16-byte aligned whenever the tensor does): float4 loads and stores when all
+// four tensors are 16-byte aligned, element-wise otherwise.  A quad lies in one plane when H*W % 4 == 0; otherwise each element finds
+// its own plane.  An output may alias its own input: a thread reads its 4 + 4 inputs before it writes, and nobody else touches them.
+// clamp: `x > 1 ? 1 : x` rather than fminf, which would drop a NaN that torch.clamp keeps.
+__global__ void __launch_bounds__(256)
+sna_batch_kernel(const float* lr, const float* hr, float* lr_out, float* hr_out, int B, uint32_t plane, const float* __restrict__ rows,
+                 unsigned flags, int vec, uint32_t k0, uint32_t k1, uint32_t off, uint32_t crop_base) {
+    const bool ori = flags & PNNP_SNA_ORI, max1 = flags & PNNP_SNA_CLIP_MAX1, min0 = flags & PNNP_SNA_CLIP_MIN0;
+    const uint32_t nquad = plane;                                  // 4 * plane elements per crop
+    const bool one_plane = (plane & 3u) == 0;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const float* R = rows + (int64_t)b * PNNP_SNA_NPARAM;      // wave-uniform: scalar loads
+        const float a0 = R[PNNP_SNA_AUG0], a1 = R[PNNP_SNA_AUG1], a2 = R[PNNP_SNA_AUG2], a3 = R[PNNP_SNA_AUG3];
+        const float K = R[PNNP_SNA_K], span = __fsub_rn(R[PNNP_SNA_WP], R[PNNP_SNA_BL]), ratio = R[PNNP_SNA_RATIO];
+        const bool active = R[PNNP_SNA_ACTIVE] != 0.f, black_lr = R[PNNP_SNA_BLACK_LR] != 0.f, add_dy = R[PNNP_SNA_ADD_DY] != 0.f;
+        const uint32_t crop = crop_base + (uint32_t)b;
+        const Ctx ctx{k0, k1, crop, off};
+        const int64_t cb = (int64_t)b * 4 * plane;
+        for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += gridDim.x * blockDim.x) {
+            const uint32_t t0 = q << 2;                            // < 2^32 (the launcher checks)
+            const int64_t base = cb + t0;
+            float l[4], h[4];
+            if (vec) {
+                const float4 lq = *reinterpret_cast<const float4*>(lr + base), hq = *reinterpret_cast<const float4*>(hr + base);
+                l[0] = lq.x; l[1] = lq.y; l[2] = lq.z; l[3] = lq.w;
+                h[0] = hq.x; h[1] = hq.y; h[2] = hq.z; h[3] = hq.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { l[i] = lr[base + i]; h[i] = hr[base + i]; }
+            }
+            if (!ori) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) l[i] = __fmul_rn(l[i], ratio);
+            }
+            if (active) {
+                const uint32_t c0 = t0 / plane;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t elem = t0 + (uint32_t)i;
+                    const int c = (int)(one_plane ? c0 : elem / plane) & 3;
+                    const float aug = c == 0 ? a0 : (c == 1 ? a1 : (c == 2 ? a2 : a3));
+                    const uint4 r = philox4x32_10(elem, crop, 0x20000000u, off, k0, k1);
+                    const float g = __fdiv_rn(__fmul_rn(h[i], span), ratio);
+                    float y = __fmul_rn(g, aug);
+                    float n = __fmul_rn(poisson_f32(__fdiv_rn(y, K), elem, ctx, r.x, r.y), K);
+                    if (black_lr) y = __fsub_rn(y, g);
+                    y = __fdiv_rn(__fmul_rn(y, ratio), span);
+                    n = __fdiv_rn(n, span);
+                    if (!ori) n = __fmul_rn(n, ratio);
+                    l[i] = __fadd_rn(l[i], n);
+                    if (add_dy) h[i] = __fadd_rn(h[i], y);
+                }
+            }
+            if (max1) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (min0) l[i] = l[i] < 0.f ? 0.f : l[i];
+                    l[i] = l[i] > 1.f ? 1.f : l[i];
+                    h[i] = h[i] < 0.f ? 0.f : h[i];
+                    h[i] = h[i] > 1.f ? 1.f : h[i];
+                }
+            }
+            if (vec) {
+                *reinterpret_cast<float4*>(lr_out + base) = make_float4(l[0], l[1], l[2], l[3]);
+                *reinterpret_cast<float4*>(hr_out + base) = make_float4(h[0], h[1], h[2], h[3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { lr_out[base + i] = l[i]; hr_out[base + i] = h[i]; }
+            }
+        }
+    }
+}
+
 // HighBitRecovery.map (data_process/process.py:718-751): re-draw every integer-valued pixel inside its quantisation
 // bin according to the read-noise distribution:  x = round(d);  if low <= x < high:  d' = ppf(cdf[x] + u * range[x]) + (d - x).
 // cdf/range: per-integer LUT built on the host with scipy (HB2LB_LUT, :697-716); dist 0 = normal(loc, scale),
@@ -509,6 +588,23 @@ extern "C" int pnnp_sna_f32(const float* gt, float* dn, float* dy, int C, int H,
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);
     hipLaunchKernelGGL(sna_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), gt, dn, dy, C, plane,
                        aug_wb4[0], aug_wb4[1], aug_wb4[2], aug_wb4[3], K, wp - bl, ratio, black_lr, ori, k0, k1, (uint32_t)offset, crop);
+    return pnnp_launch_status();
+}
+
+extern "C" int pnnp_sna_batch_f32(const float* lr, const float* hr, float* lr_out, float* hr_out, int B, int H, int W, const float* rows,
+                                  unsigned flags, uint64_t seed, uint64_t offset, uint32_t crop_base, void* stream) {
+    if (!lr || !hr || !lr_out || !hr_out || !rows || B < 0 || H < 0 || W < 0) return PNNP_E_INVALID;
+    const int64_t plane = (int64_t)H * W;
+    if (4 * plane >= (1ll << 32) || B >= (1 << 24)) return PNNP_E_INVALID;        // (element counter 32 bits; crop index as in the sampler)
+    if (B == 0 || plane == 0) return PNNP_OK;
+    // short blocks (1024 elements each), handed out dynamically: a wave's time varies with its pixels' Poisson counts
+    int64_t gx = (plane + 255) / 256;
+    if (gx > 65536) gx = 65536;
+    const int gy = B < 65535 ? B : 65535;
+    const int vec = ((((uintptr_t)lr | (uintptr_t)hr | (uintptr_t)lr_out | (uintptr_t)hr_out) & 15) == 0);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);
+    hipLaunchKernelGGL(sna_batch_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, as_stream(stream), lr, hr, lr_out, hr_out, B,
+                       (uint32_t)plane, rows, flags, vec, k0, k1, (uint32_t)offset, crop_base);
     return pnnp_launch_status();
 }
 

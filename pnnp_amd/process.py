@@ -310,10 +310,9 @@ def generate_noisy_torch(y, camera_type=None, noise_code='p', param=None, MultiF
     return out[0] if squeeze else out
 
 
-def SNA_torch(gt, aug_wb, camera_type='IMX686', ratio=1, black_lr=False, ori=True, iso=None):
-    """process.py:562-588 (shot-noise augmentation, the Mix_Dataset branch of Trainer.preprocess, trainer_SID.py:429-447)
-    on the HIP sampler: gt [4,H,W] CUDA, aug_wb the four plane gains -> (dn, dy).  The gain draw K uses numpy's
-    global RNG exactly like the reference; the Poisson draw uses the library's counter RNG (statistical parity)."""
+def _sna_params(camera_type, iso):
+    """process.py:563-571: the camera's parameters at ``iso`` with SNA_torch's K draw, ONE np.random.uniform(-0.01, 0.01) (the per-ISO
+    table's Kmax, or the SonyA7S2 regression for a camera without one); KeyError for an ISO that is not calibrated."""
     p = get_specific_noise_params(camera_type=camera_type, iso=iso)
     if p is None:
         assert camera_type == 'SonyA7S2'
@@ -322,6 +321,14 @@ def SNA_torch(gt, aug_wb, camera_type='IMX686', ratio=1, black_lr=False, ori=Tru
         p['K'] = 0.0009546 * iso * (1 + np.random.uniform(low=-0.01, high=+0.01)) - 0.00193
     else:
         p['K'] = p['Kmax'] * (1 + np.random.uniform(low=-0.01, high=+0.01))
+    return p
+
+
+def SNA_torch(gt, aug_wb, camera_type='IMX686', ratio=1, black_lr=False, ori=True, iso=None):
+    """process.py:562-588 (shot-noise augmentation, the Mix_Dataset branch of Trainer.preprocess, trainer_SID.py:429-447)
+    on the HIP sampler: gt [4,H,W] CUDA, aug_wb the four plane gains -> (dn, dy).  The gain draw K uses numpy's
+    global RNG exactly like the reference; the Poisson draw uses the library's counter RNG (statistical parity)."""
+    p = _sna_params(camera_type, iso)
     _lib.require_cuda(gt)
     g = gt.contiguous().float()
     Cc, H, W = g.shape
@@ -333,6 +340,119 @@ def SNA_torch(gt, aug_wb, camera_type='IMX686', ratio=1, black_lr=False, ori=Tru
                                        C.c_float(float(p['wp'])), C.c_float(float(p['bl'])), C.c_float(float(ratio)), int(bool(black_lr)),
                                        int(bool(ori)), C.c_uint64(_RngState.seed), C.c_uint64(off), C.c_uint32(0), _lib.stream()), 'sna')
     return dn, dy
+
+
+def get_aug_param_torch(data, b=8, command='augv5', numpy=False, camera_type='SonyA7S2'):
+    """process.py:415-445: the per-crop white-balance gain changes (aug_r, aug_g, aug_b) of the paired-data preprocess branch, on the
+    host with the reference's draws in the reference's order -- np.random.randint(2), np.random.randint(4), then for 'augv5'
+    ``random_gains`` and three torch.rand, for 'augv2' three torch.randn on the CPU generator -- so seeded runs agree.  A command that
+    names neither scheme leaves the gains zero.  The renormalisation keeps 1 + gain non-negative relative to the smallest of the three."""
+    from .augment import random_gains
+    aug_r, aug_g, aug_b = torch.zeros(b), torch.zeros(b), torch.zeros(b)
+    r = np.random.randint(2) * 0.25 + 0.25
+    u = r
+    if np.random.randint(4):
+        if 'augv5' in command:
+            rgb_gain, red_gain, blue_gain = random_gains(camera_type)
+            rgb_gain = 1 / rgb_gain
+            rg = data['wb'][:, 0] / red_gain[0]
+            bg = data['wb'][:, 2] / blue_gain[0]
+            aug_g = torch.rand(b) * r + rgb_gain[0] - 0.9
+            aug_r = torch.rand(b) * r + rg * (1 + aug_g) - 1.1
+            aug_b = torch.rand(b) * r + bg * (1 + aug_g) - 1.1
+        elif 'augv2' in command:
+            aug_g = torch.clamp(torch.randn(b) * r, 0, 4 * u)
+            aug_r = torch.clamp((1 + torch.randn(b) * r) * (1 + aug_g) - 1, 0, 4 * u)
+            aug_b = torch.clamp((1 + torch.randn(b) * r) * (1 + aug_g) - 1, 0, 4 * u)
+    daug, _ = torch.min(torch.stack((aug_r, aug_g, aug_b)), dim=0)
+    daug[daug > 0] = 0
+    aug_r = (1 + aug_r) / (1 + daug) - 1
+    aug_g = (1 + aug_g) / (1 + daug) - 1
+    aug_b = (1 + aug_b) / (1 + daug) - 1
+    if numpy:
+        aug_r, aug_g, aug_b = np.squeeze(aug_r.numpy()), np.squeeze(aug_g.numpy()), np.squeeze(aug_b.numpy())
+    return aug_r, aug_g, aug_b
+
+
+# column order of a row of the batched SNA pass (include/pnnp_hip.h: PNNP_SNA_*)
+SNA_NPARAM = 12
+SNA_K, SNA_WP, SNA_BL, SNA_RATIO, SNA_ACTIVE, SNA_BLACK_LR, SNA_ADD_DY = 4, 5, 6, 7, 8, 9, 10
+SNA_F_ORI, SNA_F_MAX1, SNA_F_MIN0 = 0x1, 0x2, 0x4
+
+
+def pack_sna_rows(aug, K, wp, bl, ratio, active, black_lr=False, add_dy=True, device='cuda'):
+    """Host values -> the f32 table [B][SNA_NPARAM] of ``sna_batch`` on ``device``: aug [B,4]; K, ratio, active [B]; wp, bl, black_lr,
+    add_dy scalars or [B].  The table lives on the device and is never read back, so what the kernel cannot report is checked here,
+    before the upload: an active row with K <= 0 or ratio <= 0 raises PnnpError.  The copy is ``non_blocking``."""
+    aug = np.asarray(aug, np.float32).reshape(-1, 4)
+    B = aug.shape[0]
+    rows = np.zeros((B, SNA_NPARAM), np.float32)
+    rows[:, :4] = aug
+    for col, v in ((SNA_K, K), (SNA_WP, wp), (SNA_BL, bl), (SNA_RATIO, ratio)):
+        rows[:, col] = np.asarray(v, np.float64)
+    for col, v in ((SNA_ACTIVE, active), (SNA_BLACK_LR, black_lr), (SNA_ADD_DY, add_dy)):
+        rows[:, col] = np.asarray(v).astype(bool)
+    bad = (rows[:, SNA_ACTIVE] != 0) & ~((rows[:, SNA_K] > 0) & (rows[:, SNA_RATIO] > 0))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _lib.PnnpError(f'sna rows: active crop {i} has K = {rows[i, SNA_K]}, ratio = {rows[i, SNA_RATIO]}; both must be > 0')
+    return torch.from_numpy(rows).to(device, non_blocking=True)
+
+
+def sna_rows(aug_wbs, ratio, iso, camera_type, black_lr, crop_per_image, add_dy=True, device='cuda'):
+    """The host half of the paired-data preprocess loop (trainer_SID.py:436-445) for a batch: aug_wbs [B,4] (host; the stacked
+    (aug_r, aug_g, aug_b, aug_g) BEFORE the ``+= 1`` of ``black_lr``, which is applied here on a copy), ratio [B] (host), iso indexed
+    ``iso[i // crop_per_image]``.  A crop is active when max|aug_wb| != 0; every ACTIVE crop, in crop order, draws its K exactly as
+    ``SNA_torch`` does (one ``np.random.uniform(-0.01, 0.01)``; an uncalibrated ISO raises KeyError), an inactive crop draws nothing.
+    -> (table [B][SNA_NPARAM] on ``device``, K float64 [B] with 0 for inactive crops)."""
+    aug = np.array(aug_wbs.detach().cpu().numpy() if torch.is_tensor(aug_wbs) else aug_wbs, np.float32).reshape(-1, 4)
+    if black_lr:
+        aug += 1
+    B = aug.shape[0]
+    ratio = (ratio.detach().cpu().numpy() if torch.is_tensor(ratio) else np.asarray(ratio)).astype(np.float32).reshape(-1)
+    ratio = np.broadcast_to(ratio, (B,)) if ratio.size == 1 else ratio
+    active = np.abs(aug).max(axis=1) != 0
+    K, wp, bl = np.zeros(B, np.float64), np.zeros(B, np.float64), np.zeros(B, np.float64)
+    for i in range(B):
+        if not active[i]:
+            continue
+        v = iso[i // crop_per_image]
+        p = _sna_params(camera_type, v.item() if hasattr(v, 'item') else v)
+        K[i], wp[i], bl[i] = p['K'], p['wp'], p['bl']
+    return pack_sna_rows(aug, K, wp, bl, ratio, active, black_lr=bool(black_lr), add_dy=bool(add_dy), device=device), K
+
+
+def sna_batch(lr, hr, rows, ori, clip, seed=None, offset=None, crop_base=0, out_lr=None, out_hr=None):
+    """The device half, one launch (csrc/noise.hip: sna_batch_kernel): lr, hr f32 [B,4,H,W] (CUDA), rows from ``sna_rows`` /
+    ``pack_sna_rows``.  Per crop: lr x ratio unless ``ori``; for an active crop the SNA_torch noise added to lr and (add_dy) the signal
+    change added to hr; then the trainer's clamp under ``clip`` (HALF_CLIP: lr <= 1 only; hr to [0,1] whenever clipping is on).
+    -> (lr_out, hr_out); ``out_lr`` / ``out_hr`` may be the inputs themselves.  Counter RNG as ``noise_sample``: the draw of crop i is
+    that of ``SNA_torch``'s entry with crop = crop_base + i and the same seed and offset."""
+    _lib.require_cuda(lr, hr, rows, out_lr, out_hr)
+    if lr.dim() != 4 or lr.shape[1] != 4 or hr.shape != lr.shape or lr.dtype != torch.float32 or hr.dtype != torch.float32:
+        raise _lib.PnnpError(f'sna_batch: lr and hr must be float32 [B,4,H,W] of one shape, got {tuple(lr.shape)} {lr.dtype}, {tuple(hr.shape)} {hr.dtype}')
+    B, _, H, W = lr.shape
+    if rows.dtype != torch.float32 or tuple(rows.shape) != (B, SNA_NPARAM) or not rows.is_contiguous():
+        raise _lib.PnnpError(f'sna_batch: rows must be contiguous float32 [{B},{SNA_NPARAM}], got {tuple(rows.shape)} {rows.dtype}')
+    out_lr = torch.empty_like(lr, memory_format=torch.contiguous_format) if out_lr is None else out_lr
+    out_hr = torch.empty_like(hr, memory_format=torch.contiguous_format) if out_hr is None else out_hr
+    for o in (out_lr, out_hr):
+        if o.shape != lr.shape or o.dtype != torch.float32 or not o.is_contiguous():
+            raise _lib.PnnpError('sna_batch: outputs must be contiguous float32 tensors of the inputs\' shape')
+    lr, hr = lr.contiguous(), hr.contiguous()
+    if seed is None:
+        seed = _RngState.seed
+    if offset is None:
+        offset = _RngState.offset
+        _RngState.offset += 1
+    flags = (SNA_F_ORI if ori else 0) | ((SNA_F_MAX1 | (0 if clip == HALF_CLIP else SNA_F_MIN0)) if clip else 0)
+    try:
+        entry = _lib.lib().pnnp_sna_batch_f32
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_sna_batch_f32: an older build of the library; rebuild it') from None
+    _lib.check(entry(_lib.ptr(lr), _lib.ptr(hr), _lib.ptr(out_lr), _lib.ptr(out_hr), B, H, W, _lib.ptr(rows), C.c_uint(flags),
+                     C.c_uint64(seed), C.c_uint64(offset), C.c_uint32(crop_base), _lib.stream()), 'sna_batch')
+    return out_lr, out_hr
 
 
 class HighBitRecovery:

@@ -27,6 +27,34 @@ from .utils import load_weights
 PROXY_DATASETS = ('NF_Syn_Dataset', 'IMX686_NF_Syn_Dataset')      # trainer_SID.py:463, trainer_LRID.py:419
 
 
+MIX_DATASETS = ('Mix_Dataset', 'IMX686_Mix_Dataset')               # trainer_SID.py:430, trainer_LRID.py:367
+SFRN_DATASETS = ('IMX686_SFRN_Raw_Dataset',)                       # trainer_LRID.py:387
+
+
+def preprocess_branch(dst):
+    """Which training branch of Trainer.preprocess a `dst_train` section selects (trainer_SID.py:428-472, trainer_LRID.py:365-427):
+    'mix' (paired frames + shot-noise augmentation), 'sfrn' (paired frames + one more exposure's shot noise), 'proxy' (NoiseFlow
+    samples) or 'physics' (the noise sampler on clean crops: every other name, as before)."""
+    name = (dst or {}).get('dataset')
+    if name in MIX_DATASETS:
+        return 'mix'
+    if name in SFRN_DATASETS:
+        return 'sfrn'
+    return 'proxy' if name in PROXY_DATASETS else 'physics'
+
+
+def synthetic_pair(hr, camera_type, generator=None):
+    """A synthetic paired batch for `--synthetic` on a paired-data run file: lr = hr / ratio plus a little Gaussian noise, the `data`
+    dictionary of the reference's loader (ratio per crop, one calibrated ISO of the camera, wb, black_lr=False) on the host."""
+    B = hr.shape[0]
+    sony = 'SonyA7S2' in camera_type
+    ratio = torch.from_numpy(np.random.uniform(100, 300, B) if sony else np.random.choice([1., 2., 4., 8., 16.], B)).float()
+    lr = (hr + 0.01 * torch.randn(hr.shape, device=hr.device, generator=generator)) / ratio.to(hr.device).view(-1, 1, 1, 1)
+    data = dict(ratio=ratio, ISO=torch.tensor([1600 if sony else 6400] * B), wb=torch.tensor([[2.0, 1.0, 1.6, 1.0]] * B),
+                black_lr=torch.tensor([False] * B))
+    return lr, data
+
+
 def build_proxy(cfg, device='cuda', allow_uninitialised_proxy=False):
     """`arch_proxy` of a run file -> the NoiseFlow proxy the train step samples from (trainer_SID.py:33-42,
     trainer_LRID.py:33-39): built by name, weights from `<fast_ckpt>/<camera>_NoiseFlow_last_model.pth`.  A missing file raises
@@ -91,7 +119,10 @@ def build(cfg, device='cuda', rank=0, world=1, group=None, allow_uninitialised_p
     archs.initialize_weights(net)                                   # trainer_SID.py:31
     net = net.to(device)
     proxy_kw = {}
-    if dst.get('dataset') in PROXY_DATASETS:                        # the preprocess branch is chosen by dst_train.dataset
+    branch = preprocess_branch(dst)
+    if branch in ('mix', 'sfrn'):                                   # paired frames: step_paired, not the physics sampler
+        proxy_kw = dict(mix=dict(command=str(dst.get('command', '')), crop_per_image=int(dst.get('crop_per_image', 1)), sfrn=branch == 'sfrn'))
+    if branch == 'proxy':                                           # the preprocess branch is chosen by dst_train.dataset
         proxy_net = build_proxy(cfg, device, allow_uninitialised_proxy)
         if proxy_net is None:
             raise KeyError('arch_proxy')                            # the reference would fail on self.proxy_net
@@ -133,7 +164,11 @@ def main(argv=None):
                 nll, sd = step.step(hr * 0.1, iso=(800, 1600, 3200)[k % 3], lr=lr)
                 losses.append(float(nll)); psnrs.append(float(sd))
                 continue
-            if step.proxy_net is not None and step.proxy_ratio_choices is not None:
+            if step.mix is not None:                                # paired-data run files: a synthetic pair through step_paired
+                hr = hr * 0.5
+                lr_in, data = synthetic_pair(hr, step.camera_type, generator=g)
+                out = step.step_paired(lr_in, hr, data, lr=lr)
+            elif step.proxy_net is not None and step.proxy_ratio_choices is not None:
                 out = step.step(hr * 0.05, lr=lr, iso=6400)         # LRID: the ISO comes with the data (trainer_LRID.py:423); 6400 = the calibrated one
             else:
                 out = step.step(hr, lr=lr)

@@ -189,7 +189,7 @@ class HipTrainStep:
     def __init__(self, net, lr=1e-4, camera_type='SonyA7S2', noise_code='pr', ori=False, clip=process.HALF_CLIP,
                  seed=1997, rank=0, world=1, group=None, bucket_bytes=8 << 20, force_reducer=False, tukey=False,
                  proxy_net=None, proxy_ratio_choices=None, proxy_iso=None, global_batch=None, overlap_allreduce=False,
-                 range_every=128, range_min_bits=16, range_max_share=1e-3, on_range_trip='warn'):
+                 range_every=128, range_min_bits=16, range_max_share=1e-3, on_range_trip='warn', mix=None):
         """``proxy_net`` (a NoiseFlow, `arch_proxy` of the run files): noise comes from ``proxy_net.sample`` instead of the
         physics sampler -- the 'NF_Syn_Dataset' branch of preprocess (trainer_SID.py:463-472: ratio ~ U(100,300) per crop,
         one random legal ISO per batch) or, with ``proxy_ratio_choices`` (dst.ratio_list), the 'IMX686_NF_Syn_Dataset'
@@ -205,7 +205,12 @@ class HipTrainStep:
         and without a host synchronisation, how far below its amax slot every element of every tensor the fp16x2 kernels split in that step
         lies; ``check_range()`` (one synchronisation, at epoch ends) reports it and acts on ``on_range_trip`` ('warn' / 'raise' /
         'fallback') when a tensor's share of elements that keep fewer than ``range_min_bits`` significand bits exceeded ``range_max_share``
-        in some census, or a tensor held inf / NaN or exceeded its slot."""
+        in some census, or a tensor held inf / NaN or exceeded its slot.
+
+        ``mix`` (None, or dict(command=, crop_per_image=, sfrn=): `dst_train.command`, `dst_train.crop_per_image` of the run files): the
+        settings of the paired-data preprocess branch that ``step_paired`` runs (``make_noisy_mix``); ``step`` does not look at it."""
+        self.mix = dict(mix) if mix is not None else None
+        self.mix_info = None
         if on_range_trip not in RANGE_TRIP_ACTIONS:
             raise ValueError(f'on_range_trip must be one of {RANGE_TRIP_ACTIONS}, got {on_range_trip!r}')
         self.range_every, self.range_min_bits, self.range_max_share, self.on_range_trip = int(range_every), int(range_min_bits), float(range_max_share), on_range_trip
@@ -340,6 +345,48 @@ class HipTrainStep:
         if not torch.is_tensor(ratio):
             ratio = torch.full((B, 1, 1, 1), ratio, device=hr.device) if self.ori else ratio
         return noisy, ratio, iso
+
+    def make_noisy_mix(self, lr_in, hr, data, command='', crop_per_image=1, sfrn=False):
+        """preprocess() on PAIRED crops with shot-noise augmentation (datasets 'Mix_Dataset', trainer_SID.py:430-447, and
+        'IMX686_Mix_Dataset', trainer_LRID.py:367-385; ``sfrn=True``: 'IMX686_SFRN_Raw_Dataset', :387-397), then the clamp (:481-485).
+        ``lr_in``, ``hr`` [B,4,H,W] (CUDA); ``data`` holds 'ratio' [B], 'ISO' (per image), 'wb' and 'black_lr' as the reference's loader
+        delivers them (host).  The host draws are the reference's in its order -- ``process.get_aug_param_torch`` (camera_type from the
+        run file, as trainer_LRID passes it), then one K per active crop -- and everything per pixel is one launch
+        (``process.sna_batch``) at counter offset ``step_count``, crops counted from this rank's first global crop.
+        ``sfrn``: gains all one with black_lr (so the noise of one more exposure is added to lr), no signal change on hr, the ISO of
+        the first image for every crop, no wb / rgb_gain update.
+        -> (noisy, hr_aug, ratio [B,1,1,1] on the device, info).  ``info``: 'wb' [B,4] (``data['wb'][0]`` per crop, times
+        (1+aug_wb[1])/(1+aug_wb) for active crops) and 'rgb_gain' [B] (1 + aug_g) -- host tensors, the reference's data['wb'] /
+        data['rgb_gain'] -- and 'K' (float64 [B], 0 for inactive crops).  ``data`` and the input tensors are not modified."""
+        if not (lr_in.is_cuda and hr.is_cuda):
+            raise PnnpError('HipTrainStep needs CUDA tensors (no CPU path)')
+        B = hr.shape[0]
+        ratio = data['ratio'].detach().reshape(-1).float().cpu()
+        info = {}
+        if sfrn:
+            aug_wbs, black, add_dy, per_image = torch.zeros(B, 4), True, False, max(B, 1)
+        else:
+            aug_r, aug_g, aug_b = process.get_aug_param_torch(data, b=B, command=command, camera_type=self.camera_type)
+            aug_wbs = torch.stack((aug_r, aug_g, aug_b, aug_g), dim=1)
+            black, add_dy, per_image = bool(data['black_lr'][0]), True, crop_per_image
+            aug = aug_wbs.numpy() + 1 if black else aug_wbs.numpy()
+            wb = data['wb'][0].repeat(B, 1)
+            for i in range(B):
+                if np.abs(aug[i]).max() != 0:
+                    wb[i] *= torch.from_numpy((1 + aug[i][1]) / (1 + aug[i]))
+            info.update(wb=wb, rgb_gain=torch.ones(B) * (aug_g + 1))
+        rows, info['K'] = process.sna_rows(aug_wbs, ratio, data['ISO'], self.camera_type, black, per_image, add_dy=add_dy, device=hr.device)
+        noisy, hr_aug = process.sna_batch(lr_in, hr, rows, self.ori, self.clip, seed=self.seed, offset=self.step_count,
+                                          crop_base=self.shard(B)[0])
+        return noisy, hr_aug, rows[:, process.SNA_RATIO].reshape(B, 1, 1, 1), info
+
+    def step_paired(self, lr_in, hr, data, lr=None):
+        """One optimiser step on a paired batch: ``make_noisy_mix`` with the constructor's ``mix`` settings, then ``step`` on its
+        result.  ``mix_info`` keeps the batch's ``info`` (the logged PSNR of the reference divides by 'rgb_gain')."""
+        if self.mix is None:
+            raise PnnpError("step_paired needs the paired-data settings: HipTrainStep(mix=dict(command=, crop_per_image=, sfrn=))")
+        noisy, hr_aug, ratio, self.mix_info = self.make_noisy_mix(lr_in, hr, data, **self.mix)
+        return self.step(hr_aug, noisy=noisy, ratio=ratio, lr=lr)
 
     def step(self, hr, plist=None, rows=None, noisy=None, lr=None, ratio=None, iso=None):
         """``ratio`` [B] (or [B,1,1,1]): the per-crop ratio for ``ori=True`` when ``noisy`` comes from outside (with the
