@@ -765,6 +765,34 @@ int pnnp_quantile_bwd_f32(int rows, int64_t n, int k, const int* arg, const floa
 int pnnp_quantile_loss_f32(const float* output, int64_t n_output, const float* gt, int64_t n_gt, int rows, const float* q, int k, void* ws,
                            float* values, int* arg, float* w, float* loss, float* dq, void* stream);
 
+/* ---------------------------------------------------------------- packed raw -> sRGB (csrc/isp.hip; data_process/process.py:104-184)
+ * The reference's pure-tensor ISP `process()` and the trainers' per-epoch preview strip, one streaming pass per pixel, one launch per call.
+ *   pnnp_isp_process_f32   in: f32 [B][4][H][W] packed RGBG (planes R, G1, B, G2), device.  rows: f32 [B][PNNP_ISP_NPARAM], device, one row per
+ *                          image: 4 white-balance gains, then the 3x3 colour matrix row-major (out[r] = sum_c ccm[r][c] in[c]).  Per pixel, in
+ *                          float32, every operation rounded on its own, in the reference's order:
+ *                            x * wb;  clamp [0,1];  g = (g1 + g2) / 2;  (r c0 + g c1) + b c2 per matrix row;  clamp [0,1];
+ *                            p = max(v, 1e-8) ^ float32(1/2.2)  (evaluated in float64 on the float32 operands, rounded once to float32; a value
+ *                            whose float32 estimate of 255 p lies further than 2e-3 from every integer keeps the estimate: the same level);
+ *                            level = clamp(int(p * 255), 0, 255)
+ *                          With PNNP_ISP_GAMMA_ONLY `in` is f32 [B][3][H][W], rows is not read (may be NULL) and only the last two lines run
+ *                          (the reference's gamma_compression).  Outputs, each optional (NULL skips it, one is required): out_f32
+ *                          f32 [B][3][H][W] = level / 255 (the reference's result); out_u8 [B][H][W][3] = level, RGB or, with PNNP_ISP_BGR, BGR.
+ *                          A NaN renders as level 0 (the reference's int() of it is undefined).
+ *   pnnp_isp_preview_f32   trainer_SID.py:150-158 / trainer_NF_SID.py:166-180: inputs, output, target: f32 [4][H][W] (device; plane 3 is not
+ *                          read); wb: 4 gains, HOST pointer; mid_offset: f32 [4][H][W] device or NULL.  out_u8 [H][3W][3] BGR: panel 0 is
+ *                          clip(inputs, 0, 1), panel 1 output (+ clip(mid_offset, 0, 1) when given), panel 2 target; channel 0 times wb[0],
+ *                          channel 2 times wb[2]; clip [0,1]; ^ float32(1/2.2) as above (no 1e-8 floor: 0 stays 0); uint8(v * 255).  Always
+ *                          clips before the power (trainer_NF_SID does; trainer_SID does not and writes NaN bytes outside [0,1]).
+ * Vector path (16 B per lane and plane, three dwords of bytes per lane) when W % 4 == 0 and every array starts 16-byte aligned; otherwise the same
+ * arithmetic with scalar accesses.  PNNP_E_INVALID: null input, no output, B, H or W < 1, B > 65535, H * ceil(W / 4) >= 2^31.
+ * These entries were added under ABI version 9 (entries only): a binding finds an older library by the missing symbol. */
+#define PNNP_ISP_NPARAM 16       /* wb[4], ccm[9], 3 unused */
+#define PNNP_ISP_BGR 0x1u        /* out_u8 in B, G, R order */
+#define PNNP_ISP_GAMMA_ONLY 0x2u /* three planes in: gamma_compression alone */
+int pnnp_isp_process_f32(const float* in, int B, int H, int W, const float* rows, unsigned flags, float* out_f32, uint8_t* out_u8, void* stream);
+int pnnp_isp_preview_f32(const float* inputs, const float* output, const float* target, const float* mid_offset, int H, int W,
+                         const float* wb /*[host, 4]*/, uint8_t* out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

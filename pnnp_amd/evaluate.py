@@ -9,9 +9,10 @@ One iteration of `SID_Trainer.eval` (trainer_SID.py:208-248; trainer_LRID.py has
     PSNR / SSIM of tensor2im(imgs_dn) and of tensor2im(imgs_lr) against tensor2im(imgs_hr), data_range 255  (:242-255)
 
 and the bookkeeping around it: the `metrics` dict that goes to `metrics.pkl` (:247,314-315: name -> [PSNR, SSIM] of the
-denoised frame, or (psnr_dn, ssim_dn) when plots are on) and the log line (:309-312).  Rendering (rawpy), plotting and
-checkpoint selection stay outside (out of scope).  The IMX686 frame 4x1736x2312 takes the padded branch
-(2312 % 16 = 8 -> 4x1744x2320).
+denoised frame, or (psnr_dn, ssim_dn) when plots are on) and the log line (:309-312).  With ``render=`` the three frames are also
+rendered to sRGB by the pure-tensor ISP (process.raw2rgb_v2, csrc/isp.hip) and scored in the RGB domain, the figures of
+plot_sample(res=None) (utils/visualization.py:55-63).  The rawpy renderer, matplotlib figures, file writing and checkpoint selection
+stay outside (out of scope).  The IMX686 frame 4x1736x2312 takes the padded branch (2312 % 16 = 8 -> 4x1744x2320).
 """
 import ctypes as C
 
@@ -23,11 +24,16 @@ from ._lib import PnnpError
 from .metrics import IlluminanceCorrect, quality_assess
 
 
-def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True):
+def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None):
     """-> dict(dn=<clamped (and corrected) prediction>, lr=<clamped input>, metrics=<device tensor [PSNR_dn, SSIM_dn, PSNR_lr, SSIM_lr]>).
 
     ``imgs_lr``, ``imgs_hr``: CUDA [1,C,H,W] (the eval loaders use batch_size 1); ``ratio``: scalar / [1] tensor, needed when
-    ``ori``.  Nothing synchronises: read ``metrics`` (``.tolist()``) when the numbers are needed."""
+    ``ori``.  Nothing synchronises: read ``metrics`` (``.tolist()``) when the numbers are needed.
+
+    ``render=dict(wb=<4 gains>, ccm=<3x3>, bgr=False)`` (C must be 4) adds ``rgb=dict(lr=, dn=, hr=)``, uint8 [H,W,3] device tensors of
+    ``lr``, ``dn`` and ``imgs_hr`` through process.raw2rgb_v2's kernel, and ``metrics_rgb``, a device tensor [PSNR_dn, SSIM_dn, PSNR_lr,
+    SSIM_lr] of ``quality_assess`` on the float renders.  ``rows=`` in the dictionary takes a table from process.isp_rows instead of
+    wb / ccm.  Still nothing synchronises; without ``render`` nothing changes."""
     if not imgs_lr.is_cuda or not imgs_hr.is_cuda:
         raise PnnpError('evaluate needs CUDA tensors (pnnp_amd has no CPU path)')
     if imgs_lr.dim() != 4 or imgs_lr.shape[0] != 1:
@@ -60,7 +66,26 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
             dn = (corrector or IlluminanceCorrect())(dn.contiguous(), imgs_hr)
         m_dn = quality_assess(dn, imgs_hr)
         m_lr = quality_assess(lr, imgs_hr) if with_lr else torch.full((2,), float('nan'), device=dn.device)
-    return dict(dn=dn, lr=lr, metrics=torch.cat([m_dn, m_lr]))
+        res = dict(dn=dn, lr=lr, metrics=torch.cat([m_dn, m_lr]))
+        if render is not None:
+            res.update(_render(render, lr, dn, imgs_hr))
+    return res
+
+
+def _render(render, lr, dn, hr):
+    """the ``render=`` part of ``evaluate``: three launches of the render kernel, two of the PSNR / SSIM kernel"""
+    from . import process
+    if lr.shape[1] != 4:
+        raise PnnpError('evaluate(render=...) needs packed RGBG frames [1,4,H,W]')
+    rows = render.get('rows')
+    if rows is None:
+        rows = process.isp_rows(render['wb'], render['ccm'], 1, lr.device)
+    bgr = bool(render.get('bgr', False))
+    f, b = {}, {}
+    for k, t in (('lr', lr), ('dn', dn), ('hr', hr)):
+        f[k], u8 = process.isp_render(t, rows, f32=True, u8=True, bgr=bgr)
+        b[k] = u8[0]
+    return dict(rgb=b, metrics_rgb=torch.cat([quality_assess(f['dn'], f['hr']), quality_assess(f['lr'], f['hr'])]))
 
 
 class AverageMeter:
@@ -90,12 +115,17 @@ class EvalLoop:
         self.metrics = {}
         self.psnr, self.ssim = AverageMeter(), AverageMeter()
         self.psnr_lr, self.ssim_lr = AverageMeter(), AverageMeter()
+        self.rgb_psnr, self.rgb_ssim = AverageMeter(), AverageMeter()                # RGB-domain meters: only steps that rendered count
+        self.rgb_psnr_lr, self.rgb_ssim_lr = AverageMeter(), AverageMeter()
         self._pending = []
+        self._pending_rgb = []
 
-    def step(self, name, imgs_lr, imgs_hr, ratio=None, epoch=-1):
+    def step(self, name, imgs_lr, imgs_hr, ratio=None, epoch=-1, render=None):
         out = evaluate(self.net, imgs_lr, imgs_hr, ratio=ratio, ori=self.ori, brightness_correct=self.brightness_correct,
-                       epoch=epoch, corrector=self.corrector)
+                       epoch=epoch, corrector=self.corrector, render=render)
         self._pending.append((name, out['metrics']))          # device tensors: one host sync per dataset, in finish()
+        if render is not None:
+            self._pending_rgb.append(out['metrics_rgb'])
         return out
 
     def finish(self, epoch=-1):
@@ -107,7 +137,15 @@ class EvalLoop:
                 self.psnr.update(p_dn); self.ssim.update(s_dn)
                 self.psnr_lr.update(p_lr); self.ssim_lr.update(s_lr)
             self._pending = []
+        if self._pending_rgb:
+            for p_dn, s_dn, p_lr, s_lr in torch.stack(self._pending_rgb).cpu().tolist():
+                self.rgb_psnr.update(p_dn); self.rgb_ssim.update(s_dn)
+                self.rgb_psnr_lr.update(p_lr); self.rgb_ssim_lr.update(s_lr)
+            self._pending_rgb = []
         text = (f"Epoch {epoch}: PSNR={self.psnr.avg:.2f}\n"
                 f"psnrs_lr={self.psnr_lr.avg:.2f}, psnrs_dn={self.psnr.avg:.2f}"
                 f"\nssims_lr={self.ssim_lr.avg:.4f}, ssims_dn={self.ssim.avg:.4f}")
+        if self.rgb_psnr.count:
+            text += (f"\nrgb: psnrs_lr={self.rgb_psnr_lr.avg:.2f}, psnrs_dn={self.rgb_psnr.avg:.2f}, "
+                     f"ssims_lr={self.rgb_ssim_lr.avg:.4f}, ssims_dn={self.rgb_ssim.avg:.4f}")
         return self.metrics, text

@@ -5,6 +5,9 @@ Host side (scalar numpy RNG, same draw order as the reference so seeded runs agr
 ``get_camera_noisy_params``, ``get_specific_noise_params``, ``sample_params_max``,
 ``sample_params``.  Device side: ``generate_noisy_obs`` / ``generate_noisy_torch`` run
 the fused HIP sampler (csrc/noise.hip); there is no CPU implementation here.
+
+Rendering (data_process/process.py:104-184): ``process``, ``raw2rgb_v2``, ``gamma_compression`` and the trainers' ``preview_strip`` run
+the render kernel (csrc/isp.hip); ``apply_gains``, ``apply_ccms``, ``raw2LRGB`` are torch ops on device tensors, not on the path.
 """
 import ctypes as C
 
@@ -524,3 +527,136 @@ def generate_noisy_obs(y, camera_type=None, wp=16383, noise_code='p', param=None
     out = noise_sample(y4, P, flags, mfm=float(MultiFrameMean) ** 0.5)
     out = out[0] if squeeze else out
     return out.cpu().numpy() if host else out
+
+
+# ---------------------------------------------------------------------------- packed raw -> sRGB (csrc/isp.hip)
+ISP_NPARAM = 16                                # PNNP_ISP_NPARAM: wb[4], ccm[9] row-major, 3 unused
+ISP_F_BGR, ISP_F_GAMMA_ONLY = 0x1, 0x2
+
+
+def apply_gains(bayer_images, wbs):
+    """process.py:104-109 as torch ops on device tensors.  Not on the path (``process`` runs one kernel and does not call this): here so
+    the reference's imports resolve and as an on-device composition to compare the kernel with."""
+    _lib.require_cuda(bayer_images, wbs)
+    N, Cc, _, _ = bayer_images.shape
+    return bayer_images * wbs.repeat((N, 1)).view(N, Cc, 1, 1)
+
+
+def apply_ccms(images, ccms):
+    """process.py:112-121 as torch ops on device tensors (see ``apply_gains``)."""
+    _lib.require_cuda(images, ccms)
+    images = images.permute(0, 2, 3, 1)[:, :, :, None, :]
+    return torch.sum(images * ccms[:, None, None, :, :], dim=-1).permute(0, 3, 1, 2)
+
+
+def raw2LRGB(bayer_images):
+    """process.py:132-139 as torch ops on device tensors (see ``apply_gains``)."""
+    _lib.require_cuda(bayer_images)
+    return torch.stack([bayer_images[:, 0, ...], torch.mean(bayer_images[:, [1, 3], ...], dim=1), bayer_images[:, 2, ...]], dim=1)
+
+
+def _check_gamma(gamma):
+    if float(gamma) != 2.2:
+        raise _lib.PnnpError(f'unsupported: gamma = {gamma}; the render kernel has the reference\'s 2.2 only')
+
+
+def isp_rows(wbs, cam2rgbs, n, device='cuda'):
+    """The parameter table of the render kernel, f32 [n][ISP_NPARAM] on ``device``: wbs [4], [1,4] (shared by all images, the reference's
+    broadcast) or [n,4]; cam2rgbs [3,3], [1,3,3] or [n,3,3]; numpy arrays or tensors on any device.  Nothing synchronises: build it once
+    per camera and pass it as ``rows=`` where a function takes it."""
+    wb = torch.as_tensor(wbs).detach().to(torch.float32).reshape(-1)
+    ccm = torch.as_tensor(cam2rgbs).detach().to(torch.float32).reshape(-1)
+    if wb.numel() not in (4, 4 * n) or ccm.numel() not in (9, 9 * n):
+        raise _lib.PnnpError(f'isp rows: wbs must hold 4 or {n}x4 gains and cam2rgbs 9 or {n}x9 entries, got {wb.numel()} and {ccm.numel()}')
+    rows = torch.zeros((n, ISP_NPARAM), dtype=torch.float32, device=wb.device)
+    rows[:, :4] = wb.reshape(-1, 4)
+    rows[:, 4:13] = ccm.reshape(-1, 9).to(wb.device)
+    return rows.to(device, non_blocking=True)
+
+
+def isp_render(images, rows=None, f32=True, u8=False, bgr=False, gamma_only=False):
+    """One launch of csrc/isp.hip over a batch: images f32 [N,4,H,W] packed RGBG (``gamma_only``: [N,3,H,W]) on the device, rows from
+    ``isp_rows``.  -> (float32 [N,3,H,W] = level / 255 or None, uint8 [N,H,W,3] RGB / BGR or None).  A non-contiguous or non-float32 input
+    is copied to a contiguous float32 tensor first; the input is never written."""
+    planes = 3 if gamma_only else 4
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != planes:
+        raise _lib.PnnpError(f'isp render: expected a tensor [N,{planes},H,W], got {tuple(images.shape) if hasattr(images, "shape") else type(images)}')
+    if not (f32 or u8):
+        raise _lib.PnnpError('isp render: no output asked for')
+    _lib.require_cuda(images, rows)
+    N, _, H, W = images.shape
+    if not gamma_only and (rows is None or rows.dtype != torch.float32 or tuple(rows.shape) != (N, ISP_NPARAM) or not rows.is_contiguous()):
+        raise _lib.PnnpError(f'isp render: rows must be contiguous float32 [{N},{ISP_NPARAM}] (process.isp_rows)')
+    x = images.detach().contiguous().float()
+    out_f = torch.empty((N, 3, H, W), dtype=torch.float32, device=x.device) if f32 else None
+    out_b = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device) if u8 else None
+    try:
+        entry = _lib.lib().pnnp_isp_process_f32
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_isp_process_f32: an older build of the library; rebuild it') from None
+    flags = (ISP_F_BGR if bgr else 0) | (ISP_F_GAMMA_ONLY if gamma_only else 0)
+    _lib.check(entry(_lib.ptr(x), N, H, W, _lib.ptr(rows), C.c_uint(flags), _lib.ptr(out_f), _lib.ptr(out_b), _lib.stream()), 'isp_process')
+    return out_f, out_b
+
+
+def process(bayer_images, wbs, cam2rgbs, gamma=2.2):
+    """process.py:142-155 in one kernel: [N,4,H,W] packed RGBG on the device -> float32 [N,3,H,W] sRGB, values k / 255.  ``wbs`` [1,4] or
+    [4] is shared by all images as in the reference; [N,4] (an extension: the reference's ``repeat`` fails there for N > 1) gives every
+    image its own gains; ``cam2rgbs`` [1,3,3] or [N,3,3].  Only gamma 2.2 has a kernel: any other value raises PnnpError('unsupported ...').
+    A NaN renders as 0 (the reference's ``.int()`` of it is undefined).  Host tensors raise PnnpError: there is no CPU implementation."""
+    _check_gamma(gamma)
+    if not torch.is_tensor(bayer_images) or bayer_images.dim() != 4 or bayer_images.shape[1] != 4:
+        raise _lib.PnnpError('process: expected a tensor [N,4,H,W] of packed RGBG planes')
+    _lib.require_cuda(bayer_images)
+    rows = isp_rows(wbs, cam2rgbs, bayer_images.shape[0], bayer_images.device)
+    return isp_render(bayer_images, rows)[0]
+
+
+def gamma_compression(images, gamma=2.2):
+    """process.py:124-129: [N,3,H,W] on the device -> clamp(int(clamp(x, min=1e-8) ** (1/2.2) * 255), 0, 255) / 255, the render kernel with
+    its front stages switched off.  Only gamma 2.2 (PnnpError('unsupported ...') otherwise)."""
+    _check_gamma(gamma)
+    return isp_render(images, gamma_only=True)[0]
+
+
+def raw2rgb_v2(packed_raw, wb, ccm, device_out=False, u8=False, bgr=False):
+    """process.py:176-184: packed raw [4,H,W] (numpy, staged through the GPU like ``isp_ops``, or a tensor), wb [4], ccm [3,3] -> numpy
+    float32 [H,W,3] like the reference, or a device tensor with ``device_out``.  ``u8=True`` returns the uint8 image [H,W,3] instead
+    (``bgr=True``: in B, G, R order, what an OpenCV writer takes)."""
+    from .isp_ops import _to_dev
+    x, _ = _to_dev(packed_raw.detach() if torch.is_tensor(packed_raw) else packed_raw)
+    if x.dim() != 3 or x.shape[0] != 4:
+        raise _lib.PnnpError(f'raw2rgb_v2: expected packed raw [4,H,W], got {tuple(x.shape)}')
+    rows = isp_rows(wb, ccm, 1, x.device)
+    out_f, out_b = isp_render(x[None], rows, f32=not u8, u8=u8, bgr=bgr)
+    out = out_b[0] if u8 else out_f[0].permute(1, 2, 0)
+    return out if device_out else out.cpu().numpy()
+
+
+def preview_strip(inputs, output, target, wb, add_inputs_to_output=False):
+    """The per-epoch preview of the trainers (trainer_SID.py:150-158; ``add_inputs_to_output``: trainer_NF_SID.py:166-180, whose middle
+    panel is sample + inputs): three device tensors [4,H,W] (or [B,4,H,W]: image 0) and the four white-balance gains (host values) ->
+    uint8 [H,3W,3] BGR on the device, panels inputs | output | target, channels R x wb[0], G1, B x wb[2], gamma 2.2.
+    Deviation: trainer_SID raises the prediction to 1/2.2 unclipped and writes NaN / wrapped bytes for values outside [0,1]; this always
+    clips first, as trainer_NF_SID does.  Inside [0,1] the two agree."""
+    ts = []
+    for name, t in (('inputs', inputs), ('output', output), ('target', target)):
+        if not torch.is_tensor(t) or t.dim() not in (3, 4) or t.shape[-3] != 4:
+            raise _lib.PnnpError(f'preview_strip: {name} must be a tensor [4,H,W] or [B,4,H,W]')
+        ts.append(t)
+    if not (ts[0].shape[-2:] == ts[1].shape[-2:] == ts[2].shape[-2:]):
+        raise _lib.PnnpError('preview_strip: the three panels must have one size')
+    _lib.require_cuda(*ts)
+    ts = [(t[0] if t.dim() == 4 else t).detach().contiguous().float() for t in ts]
+    wbv = np.asarray(wb.detach().cpu() if torch.is_tensor(wb) else wb, np.float32).reshape(-1)
+    if wbv.size != 4:
+        raise _lib.PnnpError('preview_strip: wb must hold 4 gains')
+    _, H, W = ts[0].shape
+    out = torch.empty((H, 3 * W, 3), dtype=torch.uint8, device=ts[0].device)
+    try:
+        entry = _lib.lib().pnnp_isp_preview_f32
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_isp_preview_f32: an older build of the library; rebuild it') from None
+    _lib.check(entry(_lib.ptr(ts[0]), _lib.ptr(ts[1]), _lib.ptr(ts[2]), _lib.ptr(ts[0] if add_inputs_to_output else None), H, W,
+                     (C.c_float * 4)(*[float(v) for v in wbv]), _lib.ptr(out), _lib.stream()), 'isp_preview')
+    return out

@@ -17,7 +17,7 @@ EXTRA = {'wino.hip': ['-fno-slp-vectorize'], 'conv_igemm.hip': ['-fno-slp-vector
          # wgrad_h2s: with the SLP vectoriser on, the producers' rolling refill ends in register copies that wait for the loads it has just issued: step -2.1 % where
          # the same source without it gains 1.05 % (profiles/r6/ab_wgrad_rolling.txt, part 4); round 5's source was indifferent to the flag
          'wgrad_h2s.hip': ['-fno-slp-vectorize'],
-         'noise.hip': ['-ffp-contract=off'], 'pack.hip': ['-ffp-contract=off'], 'cropaug.hip': ['-ffp-contract=off'], 'noise_score.hip': ['-ffp-contract=off'], 'ddl.hip': ['-ffp-contract=off'], 'quantile.hip': ['-ffp-contract=off'],
+         'noise.hip': ['-ffp-contract=off'], 'pack.hip': ['-ffp-contract=off'], 'isp.hip': ['-ffp-contract=off'], 'cropaug.hip': ['-ffp-contract=off'], 'noise_score.hip': ['-ffp-contract=off'], 'ddl.hip': ['-ffp-contract=off'], 'quantile.hip': ['-ffp-contract=off'],
          # the Winograd backward-weight kernel's source order is its schedule (slots fenced with sched_barrier)
          # (-fno-slp-vectorize: its stride-2 transforms vectorise into packed ops fed by 84 register moves per chunk; scalar is 44 fewer)
          'wino_wgrad.hip': ['-mllvm', '-pre-RA-sched=source'] + os.environ.get('PNNP_WW_FLAGS', '-fno-slp-vectorize').split()}
@@ -59,9 +59,11 @@ def build(verbose=True, force=False):
         run([HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + objs)
     # test / tool helper (not part of the product): the kernel that occupies k CUs beside a persistent grid (tools/squat_test.py,
     # tests/test_gpu_overlap.py) -- built HERE so that no test has to spawn hipcc from a process that has initialised the GPU
-    sq_src, sq_so = os.path.join(REPO, 'tools', 'ubench', 'squat.hip'), os.path.join(REPO, 'tools', 'ubench', 'libsquat.so')
-    if os.path.exists(sq_src) and (force or newer(sq_so, [sq_src])):
-        run([HIPCC, '--offload-arch=gfx950', '-O3', '-shared', '-fPIC', '-o', sq_so, sq_src])
+    # ... and the plain byte mover the render kernel is measured against (tools/isp_render_bench.py)
+    for name in ('squat', 'isp_roof'):
+        sq_src, sq_so = os.path.join(REPO, 'tools', 'ubench', name + '.hip'), os.path.join(REPO, 'tools', 'ubench', 'lib' + name + '.so')
+        if os.path.exists(sq_src) and (force or newer(sq_so, [sq_src])):
+            run([HIPCC, '--offload-arch=gfx950', '-O3', '-shared', '-fPIC', '-o', sq_so, sq_src])
     return OUT
 
 
