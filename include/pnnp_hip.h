@@ -793,6 +793,38 @@ int pnnp_isp_process_f32(const float* in, int B, int H, int W, const float* rows
 int pnnp_isp_preview_f32(const float* inputs, const float* output, const float* target, const float* mid_offset, int H, int W,
                          const float* wb /*[host, 4]*/, uint8_t* out_u8, void* stream);
 
+/* ---------------------------------------------------------------- sRGB -> packed raw (csrc/unprocess.hip; data_process/unprocess.py:79-167, 199-207)
+ * The reference's `unprocess()` arithmetic and its `mosaic` / `mosaic_GBRG` gathers, one streaming pass per pixel, one launch per call.
+ *   in        device; in_kind says what it holds:  PNNP_UNP_IN_HWC_F32  f32 [B][H][W][3] (the reference's layout: apply_ccm and safe_invert_gains
+ *             work on the last axis);  PNNP_UNP_IN_CHW_F32  f32 [B][3][H][W] planes;  PNNP_UNP_IN_HWC_U8  uint8 [B][H][W][3], taken as
+ *             float32(v) / 255 (an EXTENSION: the reference has no 8-bit input).
+ *   rows      f32 [B][PNNP_UNP_NPARAM], device, one row per image: rgb2cam row-major (c[i] = sum_j l[j] rgb2cam[i][j]), then the three gains
+ *             (1/red, 1, 1/blue) / rgb_gain as the reference's float32 tensor ops give them (safe_invert_gains :111), 4 unused.
+ *   Per pixel, in float32, every operation rounded on its own, in the reference's order:
+ *             x = clamp(in, 0, 1);  s = 0.5 - sin(asin(1 - 2x) / 3);  l = max(s, 1e-8) ^ 2.2;  c[i] = (l0 m[i][0] + l1 m[i][1]) + l2 m[i][2];
+ *             gray = ((c0 + c1) + c2) / 3;  mask = (max(gray - 0.9, 0) / float32(1 - 0.9))^2;  safe[i] = max(mask + (1 - mask) gains[i], gains[i]);
+ *             out[i] = clamp(c[i] safe[i], 0, 1)
+ *             DEVIATION: s is the same root of 3 s^2 - 2 s^3 = x taken without the reference's cancellation (it returns the 1e-8 floor below
+ *             x ~ 6e-8; x > 0.5 through the curve's symmetry) and polished by one Newton step with a float64 residual: within an ulp of
+ *             the float64 value for every x.
+ *             A NaN passes every clamp and the maximum as in torch: one NaN channel makes the pixel's three channels NaN.
+ *   out_rgb   f32 in the INPUT's layout ([B][H][W][3], or [B][3][H][W] for CHW_F32): what `unprocess()` returns.  NULL skips it.
+ *   out_packed  f32 [B][4][H/2][W/2], the gather of out_rgb.  NULL skips it; one output is required.  Plane order without flags (`mosaic`):
+ *             R (0::2,0::2), Gr (0::2,1::2), B (1::2,1::2), Gb (1::2,0::2), the RGBG order of raw2bayer above.  With PNNP_UNP_GBRG
+ *             (`mosaic_GBRG`, whose plane order differs): R (1::2,0::2), Gr (1::2,1::2), Gb (0::2,0::2), B (0::2,1::2).  Bitwise the gather of
+ *             out_rgb of the same launch; with out_rgb NULL a pixel applies the gain to its Bayer channel alone.
+ * Vector path (16-byte loads and RGB stores, 8-byte packed stores) when W % 4 == 0 and every array starts 16-byte aligned (uint8 input: 4);
+ * otherwise the same arithmetic with element accesses.  PNNP_E_INVALID: null in or rows, no output, an unknown in_kind or flag, B, H or W < 1,
+ * odd H or W with out_packed (the reference's torch.stack fails there), a float array that is not 4-byte aligned, B H W >= 2^40.
+ * Added under ABI version 9 (an entry only): a binding finds an older library by the missing symbol. */
+#define PNNP_UNP_NPARAM 16       /* rgb2cam[9], gains[3], 4 unused */
+#define PNNP_UNP_IN_HWC_F32 0
+#define PNNP_UNP_IN_CHW_F32 1
+#define PNNP_UNP_IN_HWC_U8 2
+#define PNNP_UNP_GBRG 0x1u       /* out_packed in mosaic_GBRG's pattern and plane order */
+int pnnp_unprocess_f32(const void* in, int in_kind, int B, int H, int W, const float* rows, unsigned flags, float* out_rgb /*or NULL*/,
+                       float* out_packed /*or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,13 +29,17 @@ PROXY_DATASETS = ('NF_Syn_Dataset', 'IMX686_NF_Syn_Dataset')      # trainer_SID.
 
 MIX_DATASETS = ('Mix_Dataset', 'IMX686_Mix_Dataset')               # trainer_SID.py:430, trainer_LRID.py:367
 SFRN_DATASETS = ('IMX686_SFRN_Raw_Dataset',)                       # trainer_LRID.py:387
+RGB_DATASETS = ('Img_Dataset',)                                    # syn_datasets.py:207: clean targets unprocessed from sRGB images
 
 
 def preprocess_branch(dst):
     """Which training branch of Trainer.preprocess a `dst_train` section selects (trainer_SID.py:428-472, trainer_LRID.py:365-427):
     'mix' (paired frames + shot-noise augmentation), 'sfrn' (paired frames + one more exposure's shot noise), 'proxy' (NoiseFlow
-    samples) or 'physics' (the noise sampler on clean crops: every other name, as before)."""
+    samples), 'rgb' (Img_Dataset: sRGB crops unprocessed to packed raw, then the noise sampler: HipTrainStep.step_rgb) or 'physics' (the
+    noise sampler on clean crops: every other name, as before)."""
     name = (dst or {}).get('dataset')
+    if name in RGB_DATASETS:
+        return 'rgb'
     if name in MIX_DATASETS:
         return 'mix'
     if name in SFRN_DATASETS:
@@ -132,7 +136,7 @@ def build(cfg, device='cuda', rank=0, world=1, group=None, allow_uninitialised_p
     step = HipTrainStep(net, lr=float(hyper['learning_rate']), camera_type=dst['camera_type'], noise_code=dst['noise_code'],
                         ori=bool(dst.get('ori', False)), clip=dst.get('clip', False), rank=rank, world=world, group=group, **proxy_kw)
     shapes = dict(batch=int(hyper.get('batch_size', 1)) * int(dst.get('crop_per_image', 1)), patch=int(dst['patch_size']),
-                  channels=int(arch['in_nc']) * int(arch.get('nframes', 1)))
+                  channels=int(arch['in_nc']) * int(arch.get('nframes', 1)), branch=branch)
     return net, step, lr_schedule(hyper), shapes
 
 
@@ -168,6 +172,9 @@ def main(argv=None):
                 hr = hr * 0.5
                 lr_in, data = synthetic_pair(hr, step.camera_type, generator=g)
                 out = step.step_paired(lr_in, hr, data, lr=lr)
+            elif sh.get('branch') == 'rgb':                         # sRGB crops of twice the packed patch, unprocessed on the device
+                rgb = torch.rand(sh['batch'], 2 * S, 2 * S, 3, device='cuda', generator=g)
+                out, _ = step.step_rgb(rgb, lr=lr)
             elif step.proxy_net is not None and step.proxy_ratio_choices is not None:
                 out = step.step(hr * 0.05, lr=lr, iso=6400)         # LRID: the ISO comes with the data (trainer_LRID.py:423); 6400 = the calibrated one
             else:

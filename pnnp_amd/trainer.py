@@ -388,6 +388,24 @@ class HipTrainStep:
         noisy, hr_aug, ratio, self.mix_info = self.make_noisy_mix(lr_in, hr, data, **self.mix)
         return self.step(hr_aug, noisy=noisy, ratio=ratio, lr=lr)
 
+    def step_rgb(self, rgb, lr=None, layout='hwc', lock_wb=False):
+        """One optimiser step on a batch of ordinary sRGB crops (device): float32 [B,H,W,3] (``layout='hwc'``) or [B,3,H,W] ('chw'), or
+        uint8 [B,H,W,3].  Every crop gets its own ``unprocess`` draw, as Img_Dataset.__getitem__ calls it once per crop
+        (syn_datasets.py:255-257; the camera is the step's, ``lock_wb=([1.], [red], [blue])`` fixes the gains); one launch of
+        csrc/unprocess.hip makes the packed RGGB target ``hr`` [B,4,H/2,W/2], then ``step(hr, lr=lr)``.
+        -> (the step's result, info): host tensors ``wb`` [B,3] = (red, 1, blue) as the dataset builds it (:257), ``ccm`` [B,3,3] = cam2rgb
+        and ``rgb_gain`` [B], what ``process.process`` / ``evaluate(render=)`` need to render the crops back."""
+        from . import unprocess as U
+        kind, B, H, W = U._check_batch(rgb, layout, 'RGGB')
+        if not rgb.is_cuda:
+            raise PnnpError('HipTrainStep needs CUDA tensors (no CPU path)')
+        draws = [U.unprocess_draw(lock_wb, self.camera_type) for _ in range(B)]
+        rgb2cam, cam2rgb, rgb_gain, red_gain, blue_gain = [torch.stack(t) for t in zip(*draws)]
+        rows = U.unprocess_rows(rgb2cam, rgb_gain, red_gain, blue_gain, B, rgb.device)
+        hr = U.unprocess_batch(rgb, rows, layout=layout, rgb=False, packed='RGGB')[1]
+        info = dict(wb=torch.cat((red_gain, torch.ones(B, 1), blue_gain), dim=1), ccm=cam2rgb, rgb_gain=rgb_gain.reshape(B))
+        return self.step(hr, lr=lr), info
+
     def step(self, hr, plist=None, rows=None, noisy=None, lr=None, ratio=None, iso=None):
         """``ratio`` [B] (or [B,1,1,1]): the per-crop ratio for ``ori=True`` when ``noisy`` comes from outside (with the
         built-in sampler it is the ratio column of the parameter rows).  ``iso``: the batch's ISO for a NoiseFlow proxy."""
