@@ -70,6 +70,10 @@ eval_post_kernel(const float* __restrict__ net_out, const float* __restrict__ lr
 __global__ void __launch_bounds__(256)
 psnr_ssim_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ partial,
                          int H, int W, float c1, float c2) {
+    // Every float32 operation below is rounded on its own.  Left to itself the compiler fuses vx / vy one way and vxy another, and
+    // A1 another way than B1: a window of two bitwise-equal images then scores 1 +- 1e-5 instead of 1 (a constant frame against
+    // itself came out as SSIM 1.0000075).  Unfused, x == y gives sxx == syy == sxy and ux == uy bit for bit, so A1 == B1 and A2 == B2.
+#pragma clang fp contract(off)
     __shared__ float xs[38][39], ys[38][39];
     __shared__ float hs[5][38][33];
     const int c = blockIdx.z, ty0 = blockIdx.y * 32, tx0 = blockIdx.x * 32;

@@ -15,6 +15,8 @@ class IlluminanceCorrect(torch.nn.Module):
 
     def forward(self, predict, source):
         _lib.require_cuda(predict, source)
+        if predict.numel() == 0:                         # (an empty batch would skip the loop below and return without a word)
+            raise _lib.PnnpError(f'illuminance_correct: empty prediction {tuple(predict.shape)}')
         predict = predict.contiguous().float(); source = source.contiguous().float()
         out = torch.empty_like(predict)
         ws = torch.empty(512, dtype=torch.float64, device=predict.device)
