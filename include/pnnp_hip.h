@@ -650,6 +650,23 @@ int pnnp_eval_post_f32(const float* net_out, const float* lr_in, float* dn, floa
 int pnnp_psnr_ssim_f32(const float* a, const float* b, float* out2 /* {psnr, ssim} */, int C, int H, int W,
                        double* workspace /* >= 2*C*ceil(H/32)*ceil(W/32) doubles */, void* stream);
 
+/* ---------------------------------------------------------------- a frame as overlapping tiles and back (csrc/tiles.hip)
+ * SynBase_Dataset.eval_crop / eval_merge (data_process/syn_datasets.py:109-159): d = base / 2, l = P - base, nh = H / l + 1, nw = W / l + 1,
+ * tile (i, j) = number i * nw + j.  Crop: tile row i, local row r reads row (i < nh - 1 ? i * l : H - l) + r of the frame reflect-padded by d
+ * (-k -> k, H-1+k -> H-1-k); the padded frame is never stored.  Merge: the interior [d, d + l) of every tile goes back to the frame; where
+ * interiors overlap, the last tile row / column owns the element (the reference's write order), and a launch stores only what its tiles own, so
+ * any partition of the tiles into launches fills the frame exactly once.  Columns alike.  Both take the tiles t0 .. t0 + nt of the grid.
+ * PNNP_E_INVALID: null pointers, base odd / <= 0 / >= P, H < l or W < l, d >= H or d >= W, a tile range outside the grid, C H W >= 2^40;
+ * crop with nhwc: Cp < C, Cp % 4 != 0, pitch < P, nhwc off a 16-byte boundary. */
+/* frame [C][H][W] -> nchw [nt][C][P][P] and / or nhwc [nt][P][pitch][Cp] (channels >= C zero-filled; the layout of pnnp_nchw_to_nhwc_f32, float4
+ * stores); amax (or null): max |element| raised into an amax slot of the fp16x2 family, as pnnp_nchw_to_nhwc_reflect_amax_f32 does. */
+int pnnp_tile_crop_f32(const float* frame, int C, int H, int W, int P, int base, int t0, int nt, float* nchw /*or null*/, float* nhwc /*or null*/,
+                       int pitch, int Cp, unsigned* amax /*or null*/, void* stream);
+/* tiles [nt][C][P][P] -> frame [C][H][W], with the eval tail on the way: frame = tile * ratio, then clamp to [0, 1] if `clamp` (a NaN stays a NaN,
+ * as in pnnp_eval_post_f32).  ratio 1 and clamp 0: the plain gather, bit for bit. */
+int pnnp_tile_merge_f32(const float* tiles, float* frame, int C, int H, int W, int P, int base, int t0, int nt, float ratio,
+                        const float* ratio_dev /*device scalar overriding ratio, or null*/, int clamp, void* stream);
+
 /* ---------------------------------------------------------------- range census of the fp16x2 family (csrc/range_census.hip)
  * Per job (a tensor an fp16x2 kernel split and the amax slot it took the scale from): an integer histogram of
  * k = floor(log2 A) - floor(log2 |x|) over the finite non-zero elements (A: the float whose bits the slot holds; bins 0 .. 46, bin 47 = k >= 47)

@@ -84,7 +84,8 @@ class _EngineBase:
         the bf16x3 backward-weight kernel is different: past it the layer falls back to the fp32 kernels: plan.py.)"""
         if not ops.x3_image_fits(H, W, cs_max):
             raise PnnpError(f'frame {H} x {W} is too large for the HIP convolution kernels: one image of a {cs_max}-channel map must stay '
-                            f'below 2 GB ((H + 4) * W * {cs_max} * 4 bytes); run the frame in tiles')
+                            f'below 2 GB ((H + 4) * W * {cs_max} * 4 bytes); run the frame in tiles: evaluate(..., tiles=dict(patch_size=...)) / '
+                            f'forward_tiled (pnnp_amd/evaluate.py)')
         return self.policy
 
     def h2_range_report(self, sample=1 << 22):
@@ -261,24 +262,34 @@ class _EngineBase:
         return jobs
 
     # ------------------------------------------------------------------ the start and end of a pass
-    def _forward_begin(self, x, train, reflect_pad, add_residual):
+    def _forward_begin(self, x, train, reflect_pad, add_residual, tile_src=None):
         """Input checks, the plan and the packs of this forward, its buffers and the activations' amax slots: (x, (B, H, W, dev), plan, bufs,
-        parameters, T).  H, W are the size the network runs on (the frame + 2 reflect_pad)."""
-        if not x.is_cuda:
+        parameters, T).  H, W are the size the network runs on (the frame + 2 reflect_pad).  With ``tile_src`` = (frame [1,C,h,w], grid, t0, nt)
+        the batch is the tiles t0 .. t0 + nt of the frame (tiles.TileGrid): B = nt, H = W = patch_size, and ``x`` comes back as the frame."""
+        if tile_src is not None:
+            x, grid, t0, nt = tile_src
+            if train or reflect_pad:
+                raise PnnpError('tile_src is an eval-mode option and excludes reflect_pad (a tile carries its own border)')
+        if not torch.is_tensor(x) or not x.is_cuda:
             raise PnnpError(f'{type(self.m).__name__}.forward: input must be a CUDA tensor (pnnp_amd has no CPU path)')
         x = x.contiguous().float()
         B, Cin, H, W = x.shape
+        if tile_src is not None:
+            if B != 1 or (H, W) != (grid.h, grid.w) or t0 < 0 or nt < 1 or t0 + nt > grid.T:
+                raise PnnpError(f'tile_src: frame {tuple(x.shape)} / tiles [{t0}, {t0 + nt}) do not match the {grid.h} x {grid.w} grid of {grid.T} tiles')
+            B, H, W = nt, grid.patch_size, grid.patch_size
         if reflect_pad:
             if train or (self.m.res and add_residual):
                 raise PnnpError('reflect_pad is an eval-mode option; a `res` network needs add_residual=False (the caller adds the input after cropping)')
             H, W = H + 2 * reflect_pad, W + 2 * reflect_pad
+        # (a frame past the kernels' size limit is told so, and where to go, whatever else is wrong with it: such a frame is rarely a multiple of 16)
+        self._pol = self.effective_policy(H, W, max(self.ch[0], self.cin_pad, self.cout_pad))
         if Cin != self.cin or H % 16 or W % 16:
             raise PnnpError(f'input must be [B,{self.cin},H,W] with H,W multiples of 16, got {tuple(x.shape)}')
         dev = x.device
         self.params.ensure(dev)
         # packed weights are re-used while no parameter changed (eval loops); in-place torch updates bump
         # tensor._version, the fused Adam kernel goes through mark_dirty()
-        self._pol = self.effective_policy(H, W, max(self.ch[0], self.cin_pad, self.cout_pad))
         plan = self._plan = self._plan_for(B, H, W, train)
         self._packs_ready(train, dev, plan)
         key = (B, H, W, dev)
@@ -289,6 +300,17 @@ class _EngineBase:
         # this step (range census)
         T = _Slots(bufs, 'f', dev, plan.h2, log={} if train else None)
         return x, key, plan, bufs, dict(self.m.named_parameters()), T
+
+    def _layout_in(self, x, x8, reflect_pad, amax, tile_src, bufs, dev):
+        """The network input's layout pass into ``x8`` (zero-padded-channel NHWC): -> (x8, the NCHW input a `res` head adds).  With ``tile_src``
+        the tile-crop kernel gathers the batch straight out of the frame ``x``; the NCHW tiles are written (same launch) only for a `res` network."""
+        if tile_src is None:
+            return ops.nchw_to_nhwc(x, x8, self.cin_pad, reflect_pad=reflect_pad, amax=amax), x
+        _, grid, t0, nt = tile_src
+        P = grid.patch_size
+        xt = bufs.get('x_tiles', (nt, self.cin, P, P), dev) if self.m.res else None
+        ops.tile_crop(x, grid, t0, nt, nchw=xt, nhwc=x8, amax=amax)
+        return x8, xt
 
     def _forward_end(self, a, key, plan, T):
         if plan.train:

@@ -70,18 +70,20 @@ class ResUnetEngine(_EngineBase):
         return '3x3', (self.cin_pad if name == 'conv_in' else None), None
 
     # ---------------------------------------------------------------- forward
-    def forward(self, x, train, reflect_pad=0, add_residual=True):
+    def forward(self, x, train, reflect_pad=0, add_residual=True, tile_src=None):
         """``reflect_pad`` > 0 (eval loop, trainer_SID.py:221-226): the network runs on the frame reflect-padded by that many pixels on
         every side -- the padding happens inside the NCHW -> NHWC layout pass, the result has the PADDED size (the caller crops).
         ``add_residual=False``: a `res` network returns f(x) without `+ x` (the caller adds the un-padded input after cropping:
-        (f(pad x) + pad x)[crop] = f(pad x)[crop] + x; pnnp_eval_post_f32)."""
-        x, key, plan, bufs, P, T = self._forward_begin(x, train, reflect_pad, add_residual)
+        (f(pad x) + pad x)[crop] = f(pad x)[crop] + x; pnnp_eval_post_f32).
+        ``tile_src=(frame [1,C,h,w], grid, t0, nt)`` (eval mode, ``x`` ignored; evaluate.forward_tiled): the batch is the tiles t0 .. t0 + nt of
+        the frame (tiles.TileGrid), gathered by the layout pass itself; the result is [nt, out_nc, patch_size, patch_size]."""
+        x, key, plan, bufs, P, T = self._forward_begin(x, train, reflect_pad, add_residual, tile_src)
         B, H, Wd, dev = key
         ch = self.ch
         g = lambda n, s: bufs.get(n, s, dev)
         hs = [H >> i for i in range(5)]; ws = [Wd >> i for i in range(5)]
         a = {}
-        a['x8'] = ops.nchw_to_nhwc(x, g('x8', (B, H, Wd, self.cin_pad)), self.cin_pad, reflect_pad=reflect_pad)
+        a['x8'], x = self._layout_in(x, g('x8', (B, H, Wd, self.cin_pad)), reflect_pad, None, tile_src, bufs, dev)
 
         def cf(name, src, src2, out, cout, act, residual=None):
             return self._conv3_fwd(plan, name, T, a, src, src2, None, out, cout, act, residual=residual)

@@ -47,20 +47,22 @@ class UNetEngine(_EngineBase):
         return self._plan['conv10_1'].fwd == 'fused'
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, train, reflect_pad=0, add_residual=True):
+    def forward(self, x, train, reflect_pad=0, add_residual=True, tile_src=None):
         """``reflect_pad`` > 0 (eval loop, trainer_SID.py:221-226): the network runs on the frame reflect-padded by that many pixels on
         every side -- the padding happens inside the NCHW -> NHWC layout pass, the result has the PADDED size (the caller crops).
         ``add_residual=False``: a `res` network returns f(x) without `+ x` (the caller adds the un-padded input after cropping:
-        (f(pad x) + pad x)[crop] = f(pad x)[crop] + x; pnnp_eval_post_f32)."""
-        x, key, plan, bufs, P, T = self._forward_begin(x, train, reflect_pad, add_residual)
+        (f(pad x) + pad x)[crop] = f(pad x)[crop] + x; pnnp_eval_post_f32).
+        ``tile_src=(frame [1,C,h,w], grid, t0, nt)`` (eval mode, ``x`` ignored; evaluate.forward_tiled): the batch is the tiles t0 .. t0 + nt of
+        the frame (tiles.TileGrid), gathered by the layout pass itself; the result is [nt, out_nc, patch_size, patch_size]."""
+        x, key, plan, bufs, P, T = self._forward_begin(x, train, reflect_pad, add_residual, tile_src)
         B, H, W, dev = key
         ch = self.ch
         g = lambda n, s: bufs.get(n, s, dev)
         a = {}
         # the zero-padded NHWC copy of the network input; its amax rides on the layout pass when conv1_1 runs on the fp16x2 kernel.  (A pooled
         # map shares its full-resolution map's amax slot.)
-        a['x8'] = T.put(ops.nchw_to_nhwc(x, g('x8', (B, H, W, self.cin_pad)), self.cin_pad, reflect_pad=reflect_pad,
-                                         amax=self._in_amax(plan, 'conv1_1', T)), 'x8', True)
+        x8, x = self._layout_in(x, g('x8', (B, H, W, self.cin_pad)), reflect_pad, self._in_amax(plan, 'conv1_1', T), tile_src, bufs, dev)
+        a['x8'] = T.put(x8, 'x8', True)
 
         def conv(name, src, src2, h, w, cout):
             return self._conv3_fwd(plan, name, T, a, src, src2, P[name + '.bias'], g(name, (B, h, w, cout)), cout, LRELU)

@@ -16,6 +16,7 @@ stay outside (out of scope).  The IMX686 frame 4x1736x2312 takes the p
 """
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -24,7 +25,60 @@ from ._lib import PnnpError
 from .metrics import IlluminanceCorrect, quality_assess
 
 
-def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None):
+def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, clamp=False):
+    """The network over one frame in overlapping tiles (the reference's eval_crop -> net per tile -> eval_merge, syn_datasets.py:109-159,
+    trainer_SID.py:209-218,351-357): CUDA [1,C,h,w] -> [1,out_nc,h,w].  The frame need not be a multiple of 16 and may be larger than
+    what one forward takes (engine.effective_policy); ``patch_size`` must be a multiple of 16 and ``h, w >= patch_size - base``.
+
+    Per chunk of ``tile_batch`` tiles (None: all of them in one batch) there is one forward, whose layout pass gathers the tiles straight
+    out of the frame (``engine.forward(tile_src=...)``: no padded frame, no NCHW tile batch), and one merge launch that writes what those
+    tiles own, optionally with ``(. * ratio).clamp(0, 1)`` fused in (``ratio``: a float or a CUDA scalar; the eval tail).  Nothing synchronises.
+
+    ``tile_batch`` only bounds the activation memory, which the engine keeps per batch shape: about ``40 * nf * patch_size^2`` bytes per
+    tile for UNetSeeInDark (ten nf-channel full-resolution maps' worth over the five levels: 0.34 GB per tile at nf = 32, patch_size = 512)
+    and about the same for ResUnet.  A last chunk of another size gets a buffer set of its own.  The result does not depend on the
+    chunking beyond what the kernels' own choices by batch size (plan.py) change: float32 rounding.
+
+    A ``net`` without a HIP engine runs as ``eval_merge(net(eval_crop(frame)))``, chunked the same way."""
+    from . import ops
+    from .tiles import TileGrid, _frame
+    x = _frame(frame, 'forward_tiled')
+    grid = TileGrid(x.shape[2], x.shape[3], patch_size, base, network=True)
+    eng = getattr(net, 'engine', None)
+    if not (eng is not None and hasattr(eng, 'forward')):
+        eng = None
+    elif x.shape[1] != eng.cin:
+        raise PnnpError(f'forward_tiled: the network takes {eng.cin} channels, the frame has {x.shape[1]}')
+    out = None
+    with torch.no_grad():
+        for t0, nt in grid.chunks(tile_batch):
+            if eng is not None:
+                y = eng.forward(None, False, tile_src=(x, grid, t0, nt))
+            else:
+                xt = torch.empty((nt, x.shape[1], grid.patch_size, grid.patch_size), dtype=torch.float32, device=x.device)
+                ops.tile_crop(x, grid, t0, nt, nchw=xt)
+                y = net(xt).contiguous().float()
+            if out is None:
+                out = torch.empty((1, y.shape[1], grid.h, grid.w), dtype=torch.float32, device=x.device)
+            ops.tile_merge(y, out, grid, t0, nt, ratio=ratio, clamp=clamp)
+    return out
+
+
+def predict(net, raw, wp, bl, patch_size, base=64, bias=None, tile_batch=None):
+    """The reference's ``predict`` (trainer_SID.py:345-360, trainer_LRID.py:341-356): a Bayer frame [H,W] (uint16 / float32, numpy or CUDA)
+    -> the denoised packed frame, a DEVICE tensor [C, H/2, W/2] (the reference saves it as .npy; writing files stays with the caller).
+    The mosaic is packed by the raw2bayer kernel with the camera's ``wp`` / ``bl`` (the reference calls raw2bayer(raw + bl) with that
+    function's defaults 1023 / 64), then ``forward_tiled`` without ratio or clamp."""
+    from . import isp_ops
+    if not torch.is_tensor(raw):
+        raw = torch.from_numpy(np.ascontiguousarray(raw))
+    if raw.dim() != 2:
+        raise PnnpError(f'predict expects one Bayer frame [H,W], got {tuple(raw.shape)}')
+    packed = isp_ops.raw2bayer(raw.cuda(), wp=wp, bl=bl, norm=True, clip=False, bias=np.zeros(4) if bias is None else bias)
+    return forward_tiled(net, packed[None], patch_size, base=base, tile_batch=tile_batch)[0]
+
+
+def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None, tiles=None):
     """-> dict(dn=<clamped (and corrected) prediction>, lr=<clamped input>, metrics=<device tensor [PSNR_dn, SSIM_dn, PSNR_lr, SSIM_lr]>).
 
     ``imgs_lr``, ``imgs_hr``: CUDA [1,C,H,W] (the eval loaders use batch_size 1); ``ratio``: scalar / [1] tensor, needed when
@@ -33,7 +87,12 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
     ``render=dict(wb=<4 gains>, ccm=<3x3>, bgr=False)`` (C must be 4) adds ``rgb=dict(lr=, dn=, hr=)``, uint8 [H,W,3] device tensors of
     ``lr``, ``dn`` and ``imgs_hr`` through process.raw2rgb_v2's kernel, and ``metrics_rgb``, a device tensor [PSNR_dn, SSIM_dn, PSNR_lr,
     SSIM_lr] of ``quality_assess`` on the float renders.  ``rows=`` in the dictionary takes a table from process.isp_rows instead of
-    wb / ccm.  Still nothing synchronises; without ``render`` nothing changes."""
+    wb / ccm.  Still nothing synchronises; without ``render`` nothing changes.
+
+    ``tiles=dict(patch_size=, base=64, tile_batch=None)``: the network runs over the frame in overlapping tiles (``forward_tiled``; the
+    reference's strategy for frames that do not fit, trainer_SID.py:209-218) instead of in one forward: the reflect-pad-4 branch is not
+    taken, the frame need not be a multiple of 16, and ``x ratio`` and the clamp of the prediction ride on the merge.  Everything behind
+    that is the same; without ``tiles`` nothing changes."""
     if not imgs_lr.is_cuda or not imgs_hr.is_cuda:
         raise PnnpError('evaluate needs CUDA tensors (pnnp_amd has no CPU path)')
     if imgs_lr.dim() != 4 or imgs_lr.shape[0] != 1:
@@ -44,6 +103,19 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
         pad = 4 if W % 16 != 0 else 0                         # :221 -- the reference tests the width only
         eng = getattr(net, 'engine', None)
         res = bool(getattr(net, 'res', False))
+        if tiles is not None:
+            if ori and ratio is None:
+                raise PnnpError('ori=True needs the ratio (trainer_SID.py:231-233)')
+            r_dev = ratio.reshape(-1)[:1].float().contiguous() if (ori and torch.is_tensor(ratio) and ratio.is_cuda) else None
+            r = 1.0 if (not ori or r_dev is not None) else float(torch.as_tensor(ratio).reshape(-1)[0])
+            dn = forward_tiled(net, lr_in, ratio=r_dev if r_dev is not None else r, clamp=True, **tiles)
+            if dn.shape != lr_in.shape:
+                raise PnnpError(f'evaluate: the network returns {tuple(dn.shape)} for a {tuple(lr_in.shape)} frame')
+            # the clamped (x ratio) input frame: the tail kernel on the frame itself, its second output not asked for
+            lr = torch.empty_like(lr_in)
+            _lib.check(_lib.lib().pnnp_eval_post_f32(_lib.ptr(lr_in), _lib.ptr(lr_in), _lib.ptr(lr), _lib.ptr(None), Cc, H, W, H, W, 0,
+                                                     C.c_float(r), _lib.ptr(r_dev), 0, _lib.stream()), 'eval_post')
+            return _evaluate_tail(dn, lr, imgs_hr, brightness_correct, epoch, corrector, with_lr, render)
         if eng is not None and hasattr(eng, 'forward'):
             # the reflection is folded into the layout pass the input goes through anyway (no F.pad kernel, no padded copy); a `res` network
             # runs without its input residual, which the tail kernel adds after the crop
@@ -62,13 +134,18 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
         dn = torch.empty_like(lr_in); lr = torch.empty_like(lr_in)
         _lib.check(_lib.lib().pnnp_eval_post_f32(_lib.ptr(out), _lib.ptr(lr_in), _lib.ptr(dn), _lib.ptr(lr), Cc, H, W, out.shape[-2], out.shape[-1], pad,
                                                  C.c_float(r), _lib.ptr(r_dev), int(add_res), _lib.stream()), 'eval_post')
-        if brightness_correct and epoch < 0:
-            dn = (corrector or IlluminanceCorrect())(dn.contiguous(), imgs_hr)
-        m_dn = quality_assess(dn, imgs_hr)
-        m_lr = quality_assess(lr, imgs_hr) if with_lr else torch.full((2,), float('nan'), device=dn.device)
-        res = dict(dn=dn, lr=lr, metrics=torch.cat([m_dn, m_lr]))
-        if render is not None:
-            res.update(_render(render, lr, dn, imgs_hr))
+        return _evaluate_tail(dn, lr, imgs_hr, brightness_correct, epoch, corrector, with_lr, render)
+
+
+def _evaluate_tail(dn, lr, imgs_hr, brightness_correct, epoch, corrector, with_lr, render):
+    """what follows the clamps in one eval iteration (trainer_SID.py:238-255): IlluminanceCorrect, the metrics, ``render=``"""
+    if brightness_correct and epoch < 0:
+        dn = (corrector or IlluminanceCorrect())(dn.contiguous(), imgs_hr)
+    m_dn = quality_assess(dn, imgs_hr)
+    m_lr = quality_assess(lr, imgs_hr) if with_lr else torch.full((2,), float('nan'), device=dn.device)
+    res = dict(dn=dn, lr=lr, metrics=torch.cat([m_dn, m_lr]))
+    if render is not None:
+        res.update(_render(render, lr, dn, imgs_hr))
     return res
 
 
@@ -106,8 +183,9 @@ class EvalLoop:
     """Accumulates what `SID_Trainer.eval` reports over a dataset: `metrics` (name -> [PSNR, SSIM], the content of
     metrics.pkl) and the log line of trainer_SID.py:309-312."""
 
-    def __init__(self, net, ori=False, brightness_correct=True):
-        self.net, self.ori, self.brightness_correct = net, ori, brightness_correct
+    def __init__(self, net, ori=False, brightness_correct=True, tiles=None):
+        """``tiles``: as in ``evaluate`` (every frame of the dataset runs in overlapping tiles); None: whole frames"""
+        self.net, self.ori, self.brightness_correct, self.tiles = net, ori, brightness_correct, tiles
         self.corrector = IlluminanceCorrect()
         self.reset()
 
@@ -122,7 +200,7 @@ class EvalLoop:
 
     def step(self, name, imgs_lr, imgs_hr, ratio=None, epoch=-1, render=None):
         out = evaluate(self.net, imgs_lr, imgs_hr, ratio=ratio, ori=self.ori, brightness_correct=self.brightness_correct,
-                       epoch=epoch, corrector=self.corrector, render=render)
+                       epoch=epoch, corrector=self.corrector, render=render, tiles=self.tiles)
         self._pending.append((name, out['metrics']))          # device tensors: one host sync per dataset, in finish()
         if render is not None:
             self._pending_rgb.append(out['metrics_rgb'])

@@ -1004,6 +1004,51 @@ def nchw_to_nhwc(src, dst, cp, reflect_pad=0, amax=None):
     return dst
 
 
+def _tile_fn(name):
+    L = _prep()
+    if not hasattr(L, name):
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no {name}: rebuild the library (tools/build.py)')
+    return getattr(L, name)
+
+
+def tile_crop(frame, grid, t0, nt, nchw=None, nhwc=None, amax=None):
+    """Tiles t0 .. t0 + nt of ``grid`` (tiles.TileGrid) out of ``frame`` [1,C,h,w] in one launch: ``nchw`` [nt,C,P,P] and / or ``nhwc``
+    [nt,P,pitch,Cp] (the zero-padded-channel layout of nchw_to_nhwc; pitch = its third dimension).  ``amax``: as in nchw_to_nhwc."""
+    require_cuda(frame, nchw, nhwc, amax)
+    _, Cc, H, W = frame.shape
+    P = grid.patch_size
+    if (H, W) != (grid.h, grid.w) or not frame.is_contiguous() or frame.dtype != torch.float32:
+        raise _lib.PnnpError(f'tile_crop: frame {tuple(frame.shape)} ({frame.dtype}) is not the contiguous float32 {grid.h} x {grid.w} frame of the grid')
+    if nchw is not None and (tuple(nchw.shape) != (nt, Cc, P, P) or not nchw.is_contiguous()):
+        raise _lib.PnnpError(f'tile_crop: nchw must be contiguous [{nt},{Cc},{P},{P}], got {tuple(nchw.shape)}')
+    pitch = cp = 0
+    if nhwc is not None:
+        if nhwc.dim() != 4 or tuple(nhwc.shape[:2]) != (nt, P) or not nhwc.is_contiguous():
+            raise _lib.PnnpError(f'tile_crop: nhwc must be contiguous [{nt},{P},pitch,Cp], got {tuple(nhwc.shape)}')
+        pitch, cp = nhwc.shape[2], nhwc.shape[3]
+    check(_tile_fn('pnnp_tile_crop_f32')(ptr(frame), Cc, H, W, P, grid.base, int(t0), int(nt), ptr(nchw), ptr(nhwc), pitch, cp, ptr(amax), stream()),
+          'tile_crop')
+
+
+def tile_merge(tiles, frame, grid, t0, nt, ratio=None, clamp=False):
+    """The interiors of tiles t0 .. t0 + nt (``tiles`` [nt,C,P,P]) into ``frame`` [1,C,h,w]: only the elements those tiles own are written.
+    ``ratio``: None, a float or a CUDA scalar tensor; ``clamp``: to [0, 1] after the product."""
+    require_cuda(tiles, frame)
+    _, Cc, H, W = frame.shape
+    P = grid.patch_size
+    if (H, W) != (grid.h, grid.w) or not frame.is_contiguous() or frame.dtype != torch.float32:
+        raise _lib.PnnpError(f'tile_merge: frame {tuple(frame.shape)} ({frame.dtype}) is not the contiguous float32 {grid.h} x {grid.w} frame of the grid')
+    if tuple(tiles.shape) != (nt, Cc, P, P) or not tiles.is_contiguous() or tiles.dtype != torch.float32:
+        raise _lib.PnnpError(f'tile_merge: tiles must be contiguous float32 [{nt},{Cc},{P},{P}], got {tuple(tiles.shape)} ({tiles.dtype})')
+    r_dev = None
+    if torch.is_tensor(ratio) and ratio.is_cuda:                   # stays on the device: nothing here synchronises
+        r_dev = ratio.reshape(-1)[:1].float().contiguous()
+    r = 1.0 if (ratio is None or r_dev is not None) else float(torch.as_tensor(ratio).reshape(-1)[0])
+    check(_tile_fn('pnnp_tile_merge_f32')(ptr(tiles), ptr(frame), Cc, H, W, P, grid.base, int(t0), int(nt), C.c_float(r), ptr(r_dev),
+                                          int(bool(clamp)), stream()), 'tile_merge')
+    return frame
+
+
 def nhwc_to_nchw(src, dst, residual=None):
     require_cuda(src, dst, residual)
     B, Cc, H, W = dst.shape
