@@ -502,6 +502,26 @@ int pnnp_l1_clamp_loss_scaled_f32(const float* pred, const float* hr, const floa
  * global batch is split unevenly over the data-parallel ranks (base_trainer.py:115-118 scatters the batch the same way); loss and SSE unweighted. */
 int pnnp_l1_clamp_loss_w_f32(const float* pred, const float* hr, const float* scale /*[B] or null*/, float* grad_nhwc, float* loss_out,
                              int B, int C, int H, int W, int Cp, float* workspace, int clamp_target, float grad_weight, void* stream);
+/* Unet_Loss (losses/base_loss.py:33-107) and its gradient (csrc/unet_loss.hip; an entry added under ABI version 9, as the tile entries were):
+ *   recon = f-mean of d = low - high, f = |d| or, with `charbonnier`, sqrt(d^2 + 1e-6); with `pyramid` the 4-level AvgPool2d(2,2) pyramid
+ *           (((t0 + t1/2) + t2/4) + t3/8) / 1.875 of the level means t_l, the levels pooled successively as Pyramid_Sample does;
+ *   total = recon + grad_lambda * grad_loss(low, high)   (the Sobel edge term, :15-31, :80-84; grad_lambda = 0: not computed).
+ * low = pred * scale[b], clamped to [0,1] when clamp_pred (the trainer's pred.clamp(0,1), trainer_SID.py:99; 0 = the bare module); high = hr,
+ * clamped when clamp_target.  Otherwise the terms of pnnp_l1_clamp_loss_w_f32: grad_weight scales the gradient only, the clamp passes gradient on
+ * the closed interval, a NaN prediction gives a NaN loss, and with charbonnier = pyramid = 0, grad_lambda = 0, clamp_pred = 1 loss, SSE and
+ * gradient are that entry's bits.
+ *   loss_out [1 + B]: total, then the per-crop SSE of the clamped pair at full resolution;  terms [5] (or null): the four level means before
+ *   weighting (levels 1-3 zero without `pyramid`) and the Sobel term;  grad_nhwc [B][H][W][Cp] (or null; Cp 4 or 8, padding channels zero) and /
+ *   or grad_nchw [B][C][H][W] (or null): dtotal/dpred.  recon = 0: only grad_lambda * the Sobel term and its gradient (SSE and terms[0..3] zero).
+ * workspace: pnnp_unet_loss_workspace_floats(B) floats, 8-byte aligned.  Deterministic: per-block partials, a one-wave finish in a fixed order.
+ * PNNP_E_INVALID before any launch, no output touched: null pred / hr / loss_out / workspace, B < 1 or > 2^20, C outside 1..8, H or W < 1,
+ * Cp < C or not 4 / 8 or grad_nhwc off a 16-byte boundary, a flag that is not 0 / 1, grad_lambda negative or not finite, recon = 0 without
+ * grad_lambda > 0, pyramid with grad_lambda > 0 (the reference never defines it), pyramid with H % 8 or W % 8 (deviation: the reference floors odd
+ * sizes; the networks need multiples of 16) or pred / hr / grad_nchw off a 16-byte boundary.  PNNP_E_WORKSPACE: workspace_floats too small. */
+int64_t pnnp_unet_loss_workspace_floats(int B);
+int pnnp_unet_loss_f32(const float* pred, const float* hr, const float* scale /*[B] or null*/, float* grad_nhwc /*or null*/, float* grad_nchw /*or null*/,
+                       float* loss_out, float* terms /*[5] or null*/, int B, int C, int H, int W, int Cp, float* workspace, int64_t workspace_floats,
+                       int clamp_target, int clamp_pred, float grad_weight, int charbonnier, int pyramid, float grad_lambda, int recon, void* stream);
 /* torch.optim.Adam step (trainer_SID.py:44,101) over a flat parameter buffer; step is 1-based;
  * grad_scale is applied to g first (1/world_size after a sum all-reduce). */
 int pnnp_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,

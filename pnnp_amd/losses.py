@@ -20,7 +20,10 @@ and the synchronisation it costs (``NoiseFlowFitStep.ddl`` does, its default poi
 statistics a row needs exactly in three streaming passes (range, a 2^15-bin census, a gather of the bins that hold a wanted rank) and a
 finish per gathered bin.  Ranks and weights follow torch's float32 rule (``pos = q * float32(N - 1)``); the probabilities need not be
 ascending, may repeat and are not read on the host.  The same tie rule, NaN and no-fallback terms as above apply, with
-1 <= N < 2^31 per row and 1 <= K <= QUANTILE_MAX_K; rows are the flattened leading dimensions."""
+1 <= N < 2^31 per row and 1 <= K <= QUANTILE_MAX_K; rows are the flattened leading dimensions.
+
+The denoiser's own loss family (losses/base_loss.py: ``Unet_Loss``, ``L1_Charbonnier_loss``, ``Pyramid_Sample``, ``Pyramid_Loss``, ``gradient``)
+is at the end of the file, on csrc/unet_loss.hip."""
 import ctypes as C
 
 import torch
@@ -368,3 +371,129 @@ def get_x(sigma=4, size=1000, mode='uniform', random=True):
             x = x + (torch.randn(size) / 2) / 10 ** sigma
         x = normal.icdf(x.clamp(tiny, 1 - tiny))
     return torch.sort(x)[0]
+
+
+# ------------------------------------------------------------------------------------------------ Unet_Loss (losses/base_loss.py:15-107)
+# The denoiser's own loss family under the reference's names.  ``Unet_Loss`` runs on csrc/unet_loss.hip (``ops.unet_loss``): forward and
+# ``.backward()`` in streaming passes, gradient with respect to ``low`` only, no clamp inside (the trainers clamp before they call it:
+# trainer_SID.py:99; ``HipTrainStep(loss=)`` folds that clamp into the kernel).  ``Pyramid_Sample``, ``Pyramid_Loss`` and ``gradient`` are plain
+# tensor ops, not on the path: kept so that the reference's imports resolve, as ``apply_gains`` is in process.py.
+# Not mirrored: ``Unet_dpsv_Loss``, ``Unet_dpsv_Loss_up`` and ``GAN_Loss`` (nothing in the reference instantiates them), the commented-out
+# ``gamma`` term of ``loss()``, the pyramid of the edge term (never defined), odd sizes under the pyramid (the reference floors; here H and W
+# must be multiples of 8 -- the networks need multiples of 16 anyway).
+
+SOBEL = ((-1.0, -2.0, -1.0), (0.0, 0.0, 0.0), (1.0, 2.0, 1.0))
+ROBERT = ((0.0, 0.0), (-1.0, 1.0))
+
+
+def gradient(maps, direction, device='cuda', kernel='sobel'):
+    """|first-derivative filter| of ``maps`` [B,C,H,W] (base_loss.py:15-31): the 3x3 Sobel (zero padding 1) or the 2x2 Robert kernel (one row of
+    zero padding above and below), expanded to a [C,C,k,k] weight, so every output channel filters the channel SUM; 'y' transposes the kernel."""
+    channels = maps.shape[1]
+    if kernel == 'robert':
+        k = torch.tensor(ROBERT).expand(channels, channels, 2, 2)
+        maps = torch.nn.functional.pad(maps, (0, 0, 1, 1))
+    elif kernel == 'sobel':
+        k = torch.tensor(SOBEL).expand(channels, channels, 3, 3)
+        maps = torch.nn.functional.pad(maps, (1, 1, 1, 1))
+    else:
+        raise ValueError(kernel)
+    if direction == 'y':
+        k = k.transpose(2, 3)
+    elif direction != 'x':
+        raise ValueError(direction)
+    return torch.nn.functional.conv2d(maps, k.to(device=device, dtype=maps.dtype)).abs()
+
+
+def Pyramid_Sample(img, max_scale=8):
+    """[AvgPool2d(2,2)(img), AvgPool2d(2,2) of that, ...] down to 1 / max_scale (base_loss.py:38-46)."""
+    out, scale = [], 2
+    while scale <= max_scale:
+        img = torch.nn.functional.avg_pool2d(img, 2, 2)
+        out.append(img)
+        scale *= 2
+    return out
+
+
+def Pyramid_Loss(lows, highs, loss_fn=torch.nn.functional.l1_loss, rate=1., norm=True):
+    """sum_i rate^i loss_fn(lows[i], highs[i]), divided by sum_i rate^i when ``norm`` (base_loss.py:48-61)."""
+    total, weights, lam = 0, 0, 1
+    for low, high in zip(lows, highs):
+        total = total + loss_fn(low, high) * lam
+        weights += lam
+        lam = lam * rate
+    return total / weights if norm else total
+
+
+def _image_pair(low, high, what):
+    for name, t in (('low', low), ('high', high)):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.PnnpError(f'{what}: {name}: expected a tensor, got {type(t).__name__}')
+    _lib.require_cuda(low, high)
+    if low.dtype != torch.float32 or high.dtype != torch.float32 or low.dim() != 4 or low.shape != high.shape or low.device != high.device:
+        raise _lib.PnnpError(f'{what}: low and high must be float32 [B,C,H,W] of one shape on one device, got {tuple(low.shape)} ({low.dtype}) '
+                             f'and {tuple(high.shape)} ({high.dtype})')
+    if not 1 <= low.shape[1] <= 8:
+        raise _lib.PnnpError(f'{what}: {low.shape[1]} channels, the kernel takes 1 .. 8')
+    return low.detach().contiguous(), high.detach().contiguous()
+
+
+class _UnetLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, low, high, charbonnier, pyramid, grad, recon):
+        from . import ops
+        lo, hi = _image_pair(low, high, 'Unet_Loss')
+        B, dev = lo.shape[0], lo.device
+        out = torch.empty(1 + B, dtype=torch.float32, device=dev)
+        terms = torch.empty(ops.UNET_LOSS_TERMS, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.unet_loss_workspace_floats(B), dtype=torch.float32, device=dev)
+        g = torch.empty_like(lo) if ctx.needs_input_grad[0] else None
+        ops.unet_loss(lo, hi, None, out, ws, clamp_pred=False, charbonnier=charbonnier, pyramid=pyramid, grad=grad, terms=terms, grad_nchw=g, recon=recon)
+        ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    def backward(ctx, gup, _):
+        g, = ctx.saved_tensors
+        return (g * gup if g is not None else None), None, None, None, None, None
+
+
+class L1_Charbonnier_loss(torch.nn.Module):
+    """mean sqrt((low - high)^2 + 1e-6) (base_loss.py:63-73) on the device."""
+
+    def __init__(self):
+        super().__init__()
+        self.eps = 1e-6
+
+    def forward(self, low, high):
+        return _UnetLoss.apply(low, high, True, False, 0.0, True)[0]
+
+
+class Unet_Loss(torch.nn.Module):
+    """base_loss.py:75-107.  ``forward(low, high, pyramid=False)``: the L1 (or, with ``charbonnier=True``, the Charbonnier) loss, plain or over the
+    4-level average-pool pyramid; ``grad_loss``: the Sobel edge term the reference keeps out of ``loss()``.  float32 CUDA tensors [B,C,H,W] with
+    C <= 8 (``PnnpError`` otherwise: no CPU path); differentiable with respect to ``low``.  ``terms`` holds the last call's terms before weighting
+    (device tensor [5]: four level means, the edge term)."""
+
+    def __init__(self, charbonnier=False):
+        super().__init__()
+        self.charbonnier = bool(charbonnier)
+        self.l1_loss = L1_Charbonnier_loss() if charbonnier else torch.nn.functional.l1_loss      # the reference's attribute; forward() does not go through it
+        self.terms = None
+
+    def _run(self, low, high, pyramid, grad, recon):
+        loss, self.terms = _UnetLoss.apply(low, high, self.charbonnier, bool(pyramid), float(grad), recon)
+        return loss
+
+    def grad_loss(self, low, high):
+        return self._run(low, high, False, 1.0, False)
+
+    def pyramid_loss(self, low, high):
+        return self._run(low, high, True, 0.0, True)
+
+    def loss(self, low, high):
+        return self._run(low, high, False, 0.0, True)
+
+    def forward(self, low, high, pyramid=False):
+        return self.pyramid_loss(low, high) if pyramid else self.loss(low, high)

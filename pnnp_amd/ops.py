@@ -1073,6 +1073,65 @@ def l1_clamp_loss(pred, hr, grad_nhwc, loss_out, ws, scale=None, clamp_target=Fa
                                            int(bool(clamp_target)), C.c_float(grad_weight), stream()), 'l1_clamp_loss')
 
 
+UNET_LOSS_KEYS = ('charbonnier', 'pyramid', 'grad')
+UNET_LOSS_TERMS = 5                                  # the four pyramid level means before weighting, then the Sobel term
+UNET_LOSS_LEVEL_WEIGHTS = (1.0, 0.5, 0.25, 0.125)    # Pyramid_Loss(rate=0.5); their sum 1.875 divides (norm=True)
+
+
+def unet_loss_options(loss):
+    """A loss setting -- a mapping with the keys ``charbonnier`` (bool), ``pyramid`` (bool), ``grad`` (the weight of the Sobel edge term, >= 0)
+    -- checked and completed with the defaults: ``HipTrainStep(loss=)``, `hyper.loss` of a run file.  Touches no device."""
+    if not hasattr(loss, 'keys'):
+        raise _lib.PnnpError(f'loss: expected a mapping with keys from {UNET_LOSS_KEYS}, got {type(loss).__name__}')
+    unknown = sorted(set(loss.keys()) - set(UNET_LOSS_KEYS))
+    if unknown:
+        raise _lib.PnnpError(f'loss: unknown keys {unknown}; the keys are {UNET_LOSS_KEYS}')
+    for k in ('charbonnier', 'pyramid'):
+        if not isinstance(loss.get(k, False), (bool, np.bool_)):
+            raise _lib.PnnpError(f'loss: {k} must be a bool, got {loss[k]!r}')
+    grad = loss.get('grad', 0.0)
+    if isinstance(grad, (bool, np.bool_)) or not isinstance(grad, (int, float, np.integer, np.floating)) or not 0.0 <= float(grad) < float('inf'):
+        raise _lib.PnnpError(f'loss: grad must be a finite number >= 0, got {grad!r}')
+    out = dict(charbonnier=bool(loss.get('charbonnier', False)), pyramid=bool(loss.get('pyramid', False)), grad=float(grad))
+    if out['pyramid'] and out['grad'] > 0:
+        raise _lib.PnnpError('loss: the Sobel edge term (grad > 0) together with the pyramid is not defined by the reference (losses/base_loss.py:80-107)')
+    return out
+
+
+def unet_loss_workspace_floats(B):
+    fn = _tile_fn('pnnp_unet_loss_workspace_floats')
+    fn.restype = C.c_int64
+    return int(fn(int(B)))
+
+
+def unet_loss(pred, hr, grad_nhwc, loss_out, ws, scale=None, clamp_target=False, grad_weight=1.0, clamp_pred=True, charbonnier=False,
+              pyramid=False, grad=0.0, terms=None, grad_nchw=None, recon=True):
+    """Unet_Loss (losses/base_loss.py:33-107) and dL/dpred in streaming passes (csrc/unet_loss.hip), beside ``l1_clamp_loss`` and with its
+    semantics for ``scale``, ``clamp_target`` and ``grad_weight``.  ``clamp_pred``: True = the trainer's call site, which passes
+    pred.clamp(0, 1) (trainer_SID.py:99); False = the bare module.  ``charbonnier`` / ``pyramid``: ``Unet_Loss(charbonnier)(low, high, pyramid)``;
+    ``grad`` > 0 adds grad * ``grad_loss`` (the Sobel edge term), which the reference keeps commented out of ``loss()``.
+    ``loss_out`` [1 + B] = [loss, sse_0 ..]; ``terms`` [5] (optional) = the level means before weighting and the Sobel term; the gradient goes to
+    ``grad_nhwc`` [B,H,W,4 or 8] and / or ``grad_nchw`` [B,C,H,W] (either may be None).  ``ws``: ``unet_loss_workspace_floats(B)`` floats.
+    ``recon=False``: the edge term alone.  With every option off: ``l1_clamp_loss``'s loss, SSE and gradient bit for bit.
+    Refused before any launch: pyramid with H % 8 or W % 8 (deviation: the reference floors odd sizes), pyramid with grad > 0."""
+    opt = unet_loss_options(dict(charbonnier=charbonnier, pyramid=pyramid, grad=grad))
+    B, Cc, H, W = pred.shape
+    if opt['pyramid'] and (H % 8 or W % 8):
+        raise _lib.PnnpError(f'unet_loss: the pyramid needs H and W to be multiples of 8, got {H} x {W}')
+    if not recon and not opt['grad'] > 0:
+        raise _lib.PnnpError('unet_loss: recon=False needs grad > 0')
+    require_cuda(pred, hr, loss_out, ws, scale, grad_nhwc, grad_nchw, terms)
+    for name, t, shape in (('pred', pred, (B, Cc, H, W)), ('hr', hr, (B, Cc, H, W)), ('grad_nchw', grad_nchw, (B, Cc, H, W)),
+                           ('grad_nhwc', grad_nhwc, (B, H, W, grad_nhwc.shape[3] if grad_nhwc is not None and grad_nhwc.dim() == 4 else -1)),
+                           ('loss_out', loss_out, (1 + B,)), ('terms', terms, (UNET_LOSS_TERMS,)), ('scale', scale, (B,))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.PnnpError(f'unet_loss: {name} must be contiguous float32 {shape}, got {tuple(t.shape)} ({t.dtype})')
+    cp = grad_nhwc.shape[3] if grad_nhwc is not None else 0
+    check(_tile_fn('pnnp_unet_loss_f32')(ptr(pred), ptr(hr), ptr(scale), ptr(grad_nhwc), ptr(grad_nchw), ptr(loss_out), ptr(terms), B, Cc, H, W, cp,
+                                         ptr(ws), _i64(ws.numel()), int(bool(clamp_target)), int(bool(clamp_pred)), C.c_float(grad_weight),
+                                         int(opt['charbonnier']), int(opt['pyramid']), C.c_float(opt['grad']), int(bool(recon)), stream()), 'unet_loss')
+
+
 def adam_step(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     require_cuda(p, g, m, v)
     check(_prep().pnnp_adam_step_f32(ptr(p), ptr(g), ptr(m), ptr(v), _i64(p.numel()), C.c_float(lr), C.c_float(beta1),

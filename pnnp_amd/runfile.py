@@ -6,6 +6,7 @@ The trainers read them with `yaml.load` and pull the hot-path settings out of th
     arch:       name, in_nc, out_nc, nf, nframes, res            -> the denoiser class in `archs`
     dst_train:  camera_type, noise_code, ori, clip, patch_size, crop_per_image, wp, bl, ratio_list
     hyper:      learning_rate, batch_size, last_epoch, stop_epoch, step_size, T      -> Adam + cosine restarts
+                loss: {charbonnier, pyramid, grad}   (extension, optional)           -> the Unet_Loss variant of the step
 
 `build(cfg)` turns an (unmodified) run file into the device pipeline: the network by name, the fused
 `HipTrainStep` and the per-epoch learning rate.  Datasets, checkpoints and logging are outside the hot path
@@ -133,8 +134,11 @@ def build(cfg, device='cuda', rank=0, world=1, group=None, allow_uninitialised_p
         proxy_kw = dict(proxy_net=proxy_net)
         if dst['dataset'] == 'IMX686_NF_Syn_Dataset':               # trainer_LRID.py:33: legal_ratio = [1, 2, 4, 8, 16]
             proxy_kw['proxy_ratio_choices'] = (1, 2, 4, 8, 16)
+    # extension (the reference's run files carry no such key; its users edit `Unet_Loss()` in the trainer instead): hyper.loss, a mapping
+    # with the keys charbonnier, pyramid, grad -> HipTrainStep(loss=), which checks it
     step = HipTrainStep(net, lr=float(hyper['learning_rate']), camera_type=dst['camera_type'], noise_code=dst['noise_code'],
-                        ori=bool(dst.get('ori', False)), clip=dst.get('clip', False), rank=rank, world=world, group=group, **proxy_kw)
+                        ori=bool(dst.get('ori', False)), clip=dst.get('clip', False), rank=rank, world=world, group=group,
+                        loss=hyper.get('loss'), **proxy_kw)
     shapes = dict(batch=int(hyper.get('batch_size', 1)) * int(dst.get('crop_per_image', 1)), patch=int(dst['patch_size']),
                   channels=int(arch['in_nc']) * int(arch.get('nframes', 1)), branch=branch)
     return net, step, lr_schedule(hyper), shapes

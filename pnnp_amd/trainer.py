@@ -189,7 +189,7 @@ class HipTrainStep:
     def __init__(self, net, lr=1e-4, camera_type='SonyA7S2', noise_code='pr', ori=False, clip=process.HALF_CLIP,
                  seed=1997, rank=0, world=1, group=None, bucket_bytes=8 << 20, force_reducer=False, tukey=False,
                  proxy_net=None, proxy_ratio_choices=None, proxy_iso=None, global_batch=None, overlap_allreduce=False,
-                 range_every=128, range_min_bits=16, range_max_share=1e-3, on_range_trip='warn', mix=None):
+                 range_every=128, range_min_bits=16, range_max_share=1e-3, on_range_trip='warn', mix=None, loss=None):
         """``proxy_net`` (a NoiseFlow, `arch_proxy` of the run files): noise comes from ``proxy_net.sample`` instead of the
         physics sampler -- the 'NF_Syn_Dataset' branch of preprocess (trainer_SID.py:463-472: ratio ~ U(100,300) per crop,
         one random legal ISO per batch) or, with ``proxy_ratio_choices`` (dst.ratio_list), the 'IMX686_NF_Syn_Dataset'
@@ -208,7 +208,15 @@ class HipTrainStep:
         in some census, or a tensor held inf / NaN or exceeded its slot.
 
         ``mix`` (None, or dict(command=, crop_per_image=, sfrn=): `dst_train.command`, `dst_train.crop_per_image` of the run files): the
-        settings of the paired-data preprocess branch that ``step_paired`` runs (``make_noisy_mix``); ``step`` does not look at it."""
+        settings of the paired-data preprocess branch that ``step_paired`` runs (``make_noisy_mix``); ``step`` does not look at it.
+
+        ``loss`` (None, or dict(charbonnier=False, pyramid=False, grad=0.0)): None is the reference's ``Unet_Loss()`` as both trainers
+        instantiate it, the L1 of ``ops.l1_clamp_loss``.  A mapping selects the rest of the family (losses/base_loss.py:33-107; ``ops.unet_loss``):
+        the Charbonnier form, the 4-level pyramid, and ``grad`` times the Sobel edge term ``grad_loss``, at the same call site, with the same
+        ``[loss, sse_0 ..]`` result; the terms before weighting are ``loss_terms`` (device tensor [5], no synchronisation) after every step.
+        Checked here: unknown keys and ``grad > 0`` with ``pyramid`` raise.  The pyramid needs crops whose H and W are multiples of 8."""
+        self.loss_opt = ops.unet_loss_options(loss) if loss is not None else None
+        self.loss_terms = None
         self.mix = dict(mix) if mix is not None else None
         self.mix_info = None
         if on_range_trip not in RANGE_TRIP_ACTIONS:
@@ -438,7 +446,13 @@ class HipTrainStep:
         lws = bufs.get('loss_ws', (128 * B,), dev)
         # trainer_SID.py:485: the target is clamped under dst.clip, in the kernel; uneven shards of a global batch: this rank's mean
         # gradient counts B_local / B_global (x world: Adam divides the all-reduced sum by world) -- folded into the kernel's gradient scale
-        ops.l1_clamp_loss(pred, hr, g8, loss, lws, scale=scale, clamp_target=bool(self.clip), grad_weight=self.shard(B)[1])
+        if self.loss_opt is None:
+            ops.l1_clamp_loss(pred, hr, g8, loss, lws, scale=scale, clamp_target=bool(self.clip), grad_weight=self.shard(B)[1])
+        else:                                                # the rest of Unet_Loss: same call site, same outputs, plus the terms
+            uws = bufs.get('unet_loss_ws', (ops.unet_loss_workspace_floats(B),), dev)
+            self.loss_terms = bufs.get('loss_terms', (ops.UNET_LOSS_TERMS,), dev)
+            ops.unet_loss(pred, hr, g8, loss, uws, scale=scale, clamp_target=bool(self.clip), grad_weight=self.shard(B)[1], clamp_pred=True,
+                          terms=self.loss_terms, **self.loss_opt)
         if self.reducer is not None:
             self.reducer.reset()
         prev_split = None
