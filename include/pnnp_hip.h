@@ -258,6 +258,30 @@ int pnnp_conv3x3_h2_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x
 int pnnp_conv3x3_h2_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
                                  const void* w_h2, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
                                  unsigned* amax_y /*or null*/, unsigned* bits_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
+/* ---- the fp16x1 ("h1") family: the same stride-1 3x3 FORWARD layers with ONE scaled fp16 piece per float32 operand (csrc/conv_h1s.hip): hi = f16(a 2^se),
+ * se from the tensor's amax slot as above; one fp16 rounding per operand (relative 2^-11), products exact, float32 accumulation -- outputs at about 1e-3
+ * relative to the activations' scale.  EVAL FORWARD ONLY and opt-in (ConvPolicy.h1_eval): no sign bits, no backward entries; five matrix instructions per
+ * chunk and block where the fp16x2 kernel issues fourteen.  Each entry has the argument list of its h2 twin minus bits_y, the same tile rule
+ * (pnnp_h2_tile_columns), split-K policy (pnnp_h2_splitk) and amax contract.  Weights: kind-7 packs of pnnp_h1_weight_bytes(K, N) bytes
+ * ([N/32][K16][tap 10][octet 2][32][8] fp16, the tenth tap and the padded K rows zero), scaled with the weight tensor's slot like the h2 pack.  Every pointer
+ * the kernels touch with vector accesses must be 16-byte aligned (x1, x2, w_h1, bias, residual, y, pooled, ws), slots and head tensors 4-byte: PNNP_E_INVALID /
+ * PNNP_E_UNSUPPORTED otherwise, nothing launched. */
+int pnnp_h1_supported(int K, int N);
+int64_t pnnp_h1_weight_bytes(int K, int N);
+int pnnp_pack_jobs_add_h1(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, int Cin_pad, const unsigned* amax_w);
+int pnnp_conv3x3_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
+                            const void* w_h1, const unsigned* amax_w, const float* bias, const float* residual, float* y,
+                            unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv3x3_h1_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
+                                   const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
+                                   int B, int H, int W, int Cout, int act, int ksplit, float* ws, int64_t ws_floats, void* stream);
+int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
+                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y /*or null*/, unsigned* amax_y,
+                                 const float* head_w, const float* head_b /*or null*/, const float* head_res /*or null*/, float* head_out,
+                                 int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
+                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
+                                 unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
 int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, const unsigned* bits1, int mode1, int accum1, unsigned* amax_dx1,
                                  float* dx2 /*or null*/, int C2, const float* mask2, const unsigned* bits2, int mode2, int accum2, unsigned* amax_dx2,

@@ -60,7 +60,7 @@ class _EngineBase:
         if policy is None:
             cur = dict(wino=self.policy.wino, wino_wgrad=self.policy.wino_wgrad, wino_mink=self.policy.wino_mink, x3=self.policy.x3,
                        thin=self.policy.thin, pool_fused=self.policy.pool_fused, h2=self.policy.h2)
-            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
+            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
                 if k in kw:
                     self._h2_sub[k] = bool(kw.pop(k))
             if 'unpool_levels' in kw:                              # which encoder levels unpool_fused applies to (plan.py)
@@ -246,6 +246,9 @@ class _EngineBase:
             taps = w.shape[2] * w.shape[3]
             cip, cop = cip or ci, cop or co
             got, slot = {}, None
+            if pf == 'h1':                             # (eval plans under h1_eval) the one-piece forward pack; no backward-data pack exists
+                got['h1'] = (b(':h1f', ops.h1_weight_bytes(cip, co)), None)
+                slot = jobs.add_h1(w, got['h1'][0], cin_pad=(cip + 15) // 16 * 16)
             if 'h2' in (pf, pd):                       # the fp16x2 kernel takes what bf16x3 would have taken
                 got['h2'] = (b(':h2f', ops.h2_weight_bytes(cip, co)) if pf == 'h2' else None, b(':h2d', ops.h2_weight_bytes(co, ci)) if pd == 'h2' else None)
                 slot = jobs.add_h2(w, *got['h2'], cin_pad=(cip + 15) // 16 * 16)
@@ -337,7 +340,7 @@ class _EngineBase:
     # of the pass / of the forward's activations; a: the forward's activations, where the sign-bit images live as 'bits:' + layer)
     def _in_amax(self, plan, name, T):
         """the slot the input's layout pass fills: only an fp16x2 first layer splits the network input"""
-        return T.slot('x8') if plan[name].fwd == 'h2' else None
+        return T.slot('x8') if plan[name].fwd in ('h2', 'h1') else None
 
     def _bits(self, plan, name, T, a, y, cout, act):
         """the sign-bit image an fp16x2 forward writes beside an activation output in a training forward"""
@@ -350,6 +353,16 @@ class _EngineBase:
     def _conv3_fwd(self, plan, name, T, a, x1, x2, bias, y, cout, act, residual=None, fill=None):
         """``fill``: x1 has no amax yet (no producer with a fused one): an fp16x2 layer fills slot ``fill`` with a launch of its own first"""
         s, (f, _, wslot) = plan[name], self._wp[name]
+        if s.fwd in ('h1', 'h1+splitk'):                     # (eval only: no sign bits) the fp16x1 twins of the two launches below
+            if fill is not None:
+                T.put(x1, fill, fused=False)
+            ax2 = T.of(x2) if x2 is not None else None
+            if s.fwd == 'h1+splitk':
+                ops.conv_h1_fwd_splitk(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev),
+                                       amax_x2=ax2, amax_y=T.slot(name))
+            else:
+                ops.conv_h1_fwd(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), ax2, amax_y=T.slot(name), residual=residual)
+            return T.put(y, name, fused=True)
         if s.fwd in ('h2', 'h2+splitk'):
             bits = self._bits(plan, name, T, a, y, cout, act) if residual is None else None
             if fill is not None:
@@ -385,6 +398,9 @@ class _EngineBase:
             ops.conv_h2_fwd_pool(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name),
                                  bits_y=self._bits(plan, name, T, a, y, cout, act))
             T.put(y, name, fused=True)
+        elif s.fwd == 'h1+pool':
+            ops.conv_h1_fwd_pool(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name))
+            T.put(y, name, fused=True)
         elif s.fwd == 'x3+pool':
             # the layer writes the pooled map and the codes from its own epilogue (csrc/conv_x3s.hip)
             ops.conv_x3_fwd_pool(x, None, f, bias, y, pooled, codes, cout, act)
@@ -404,6 +420,9 @@ class _EngineBase:
         # both layers in one kernel (csrc/conv_h2s.hip EK_HEAD): the output planes come straight from the accumulators; the 3x3 layer's map
         # is stored (with its sign bits and amax) only for a backward pass -- an eval forward neither writes nor re-reads it
         f, _, wslot = self._wp[name]
+        if plan[name].fwd == 'h1+head':                      # (eval only: the 32-channel map is never stored)
+            ops.conv_h1_fwd_head(x, None, f, wslot, bias, None, yshape[3], act, T.of(x), hw, hb, out, residual=res)
+            return None
         y = T.bufs.get(name, yshape, T.dev) if plan.train else None
         ops.conv_h2_fwd_head(x, None, f, wslot, bias, y, yshape[3], act, T.of(x), hw, hb, out, amax_y=T.slot(name) if plan.train else None,
                              bits_y=self._bits(plan, name, T, a, y, yshape[3], act), residual=res)

@@ -5,7 +5,9 @@ and launch nothing (the shape predicates they ask are host functions of libpnnp_
 without a GPU.  The engines build their weight packs and issue their launches from the returned Plan; a backward pass uses the plan of
 its own forward.  Families: 'h2' (fp16x2), 'x3' (bf16x3), 'wino' (Winograd), 'direct' (fp32 implicit GEMM), 'thin' (the streaming
 4-channel ends); a forward may carry a fused variant ('h2+pool', 'x3+pool', 'h2+splitk', 'h2+head'; conv10_1 is then 'fused'), and
-ResUnet's identity-shortcut backward-data 'FAMILY+res'.  None: the pass does not run (eval, or no gradient w.r.t. the input)."""
+ResUnet's identity-shortcut backward-data 'FAMILY+res'.  None: the pass does not run (eval, or no gradient w.r.t. the input).
+'h1' (fp16x1, csrc/conv_h1s.hip) exists in EVAL plans only, under ``ConvPolicy.h1_eval``: the stride-1 3x3 layers whose forward would
+be 'h2' / 'h2+pool' / 'h2+splitk' / 'h2+head' take the same variant of 'h1'; everything else in the plan stays as it is."""
 import os
 
 from .. import ops
@@ -40,13 +42,17 @@ class ConvPolicy:
         # its own; ``unpool_levels``: the encoder levels (1 = the full-resolution one .. 4) it applies to -- PNNP_UNPOOL_LEVELS=234 keeps level 1 on the pass
         self.unpool_fused = bool(h2) and os.environ.get('PNNP_UNPOOL_FUSED', '1') != '0'
         self.unpool_levels = tuple(sorted({int(c) for c in os.environ.get('PNNP_UNPOOL_LEVELS', '1234') if c in '1234'}))
+        # (opt-in, off by default) EVAL forwards run the stride-1 3x3 layers that are on fp16x2 with ONE fp16 piece per operand instead (csrc/conv_h1s.hip:
+        # one rounding per operand, float32 accumulation, ~1e-3 of the activations' scale; 5 matrix instructions per chunk where fp16x2 issues 14).  Only
+        # meaningful with ``h2``; a training plan ignores it.  Not part of key(): the packs are keyed by the plan's pack families ('h1')
+        self.h1_eval = bool(h2) and os.environ.get('PNNP_H1_EVAL', '0') != '0'
 
     def key(self):
         return (self.wino, self.wino_wgrad, self.wino_mink, self.x3, self.thin, self.pool_fused, self.h2, self.h2_wgrad, self.h2_pointwise, self.head_fused, self.splitk, self.convt_bits)
 
     def plan_key(self):
         """What a cached Plan depends on: key() (the families and packs) + the switches that only change the launch sequence."""
-        return self.key() + (self.unpool_fused, self.unpool_levels)
+        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval)
 
     def use_thin_head(self, cin, cout, npix):
         return self.thin and ops.head_supported(cin, cout, npix)
@@ -132,6 +138,16 @@ class Plan:
     def table(self):
         return {n: s.families() for n, s in self.steps.items()}
 
+    def to_h1(self, names):
+        """(eval plans, ConvPolicy.h1_eval) the layers ``names`` whose forward is an fp16x2 3x3 launch take the fp16x1 kernel: same variant, pack family
+        'h1'.  ``h2`` stays as it was: the amax slots are what the scale is made of, and the pointwise layers stay on fp16x2."""
+        for n in names:
+            s = self.steps[n]
+            if s.fwd in ('h2', 'h2+pool', 'h2+splitk', 'h2+head'):
+                s.fwd, s.pack = 'h1' + s.fwd[2:], ('h1', s.pack[1])
+        self.packs = tuple(s.pack for s in self.steps.values())
+        return self
+
 
 def _pad8(c):
     return (c + 7) // 8 * 8
@@ -208,6 +224,8 @@ def resolve_unet(ch, cin, cout, pol, train, B, H, W):
                 s.fwd = 'h2+splitk'
     if pol.head_fused and ch[0] == 32 and cout == 4 and st['conv9_2'].fwd.startswith('h2'):
         st['conv9_2'].fwd, st['conv9_2'].ks, st['conv10_1'].fwd = 'h2+head', 1, 'fused'
+    if not train and pol.h1_eval and pol.h2:
+        plan.to_h1([f'conv{i}_{j}' for i in range(1, 10) for j in (1, 2)])
     if train:
         for i in range(6, 10):             # the skip gradient of conv{i}_1 + MaxPool2d backward in one epilogue: needs the skip tensor's sign bits and codes
             skip = st[f'conv{10 - i}_2']
@@ -268,6 +286,8 @@ def resolve_resunet(ch, cin, cout, pol, train, B, H, W):
     if thin_first:
         st['conv_in'].fwd = 'thin'
     if not train:
+        if pol.h1_eval and pol.h2:
+            plan.to_h1(['conv_in'] + [f'b{i}_{j}' for i in range(1, 10) for j in (0, 1)])
         return plan
     for l in range(1, 6):
         st[f'b{l}_0'].dgrad += '+res'                  # identity shortcut: d/d(input) = dgrad(block) + g in one kernel

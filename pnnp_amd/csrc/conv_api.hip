@@ -298,6 +298,67 @@ int pnnp_conv3x3_h2_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x
     return pnnp_igemm_h2s_launch(a, C1, as_stream(stream));
 }
 
+// ---------------------------------------------------------------- the same forward layers with ONE fp16 piece per operand (fp16x1, csrc/conv_h1s.hip)
+// Eval forward only: the h2 entries' contracts without sign bits; w_h1: the kind-7 pack (pnnp_pack_jobs_add_h1).  Alignment of every pointer a kernel touches
+// with vector accesses is checked here or in the launcher (csrc/conv_s.h conv_s_validate): y, bias and the workspace of the split-K entry included.
+int pnnp_h1_supported(int K, int N) { return pnnp_h2_supported(K, N); }
+
+int pnnp_conv3x3_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
+                            const void* w_h1, const unsigned* amax_w, const float* bias, const float* residual, float* y,
+                            unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w_h1 || !y || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, residual, y, B, H, W, Cout, act);
+    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;
+    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+}
+
+int pnnp_conv3x3_h1_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
+                                   const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
+                                   int B, int H, int W, int Cout, int act, int ksplit, float* ws, int64_t ws_floats, void* stream) {
+    if (ksplit <= 1) return pnnp_conv3x3_h1_fwd_f32(x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, nullptr, y, amax_y, B, H, W, Cout, act, stream);
+    if (!x1 || !w_h1 || !y || !ws || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (Cout & 31)) return PNNP_E_INVALID;
+    // (the reduce kernel reads the slabs and the bias and writes y as float4; the slot takes an atomicMax)
+    if (((((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)ws)) & 15) || (((uintptr_t)amax_y) & 3)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    if (ws_floats < (int64_t)ksplit * B * H * W * Cout) return PNNP_E_WORKSPACE;
+    if ((int64_t)ksplit * B >= (1 << 20)) return PNNP_E_UNSUPPORTED;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w_h1, nullptr, nullptr, ws, B, H, W, Cout, 0);
+    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w;
+    a.ksplit = ksplit;
+    const int rc = pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+    if (rc != PNNP_OK) return rc;
+    return pnnp_h2_splitk_reduce_launch(ws, ksplit, bias, y, nullptr, amax_y, B, H, W, Cout, act, as_stream(stream));
+}
+
+int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
+                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
+                                 const float* head_w, const float* head_b, const float* head_res, float* head_out,
+                                 int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w_h1 || !head_w || !head_out || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (Cout != 32) return PNNP_E_UNSUPPORTED;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, nullptr, y, B, H, W, Cout, act);
+    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = y ? amax_y : nullptr;
+    a.head_w = head_w; a.head_b = head_b; a.head_res = head_res; a.head_out = head_out;
+    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+}
+
+int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
+                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
+                                 unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w_h1 || !y || !pooled || !codes || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (H & 1) || (W & 1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, nullptr, y, B, H, W, Cout, act);
+    a.g.pool_dst = pooled; a.g.pool_codes = codes; a.g.pool_cs = Cout;
+    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;      // (the pooled map is a subset of y)
+    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+}
+
 // mask1 / mask2: the float32 activation, or bits1 / bits2: its sign bits from the forward kernel (then the float32 pointer is not read)
 int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, const unsigned* bits1, int mode1, int accum1, unsigned* amax_dx1,

@@ -9,6 +9,7 @@
 //   job kind 4: 3x3 filters scaled by a power of two and split into two fp16 pieces for csrc/conv_h2s.hip (the scale comes from the amax slot
 //               that a kind-5 job of an EARLIER launch filled)
 //   job kind 5: max |src| -> atomicMax into a 4-byte slot (csrc/h2.h)
+//   job kind 7: 3x3 filters scaled like kind 4 and rounded to ONE fp16 piece for csrc/conv_h1s.hip (forward orientation only)
 // The builders below produce exactly the jobs the per-layer entry points used to launch (same formulas, same layouts).
 #include "common.h"
 #include "h2.h"
@@ -205,6 +206,38 @@ __device__ __forceinline__ void h2_job(const PnnpPackJob& j, int64_t blk, int nb
     }
 }
 
+// fp16x1 pack of a 3x3 Conv2d weight for csrc/conv_h1s.hip:  dst (fp16) [N/32][K16] x hi' [tap 10][octet 2][32][8]  (the tenth tap is ZERO: the partner of
+//   the unpaired ninth tap; 10240 bytes per 32-column block and chunk).  Forward orientation only: element (k, n, tap) = w[n][k][tap] (K = Cin, N = Cout);
+//   hi' = f16(W s), s = 2^pnnp_h2_scale_exp(*amax) as in h2_job (round to nearest even); k >= Cin (padding up to Kvalid) and n >= Cout -> 0.
+//   job: K = Cout, N = Cin, Kvalid = padded K, amax = the slot.  One thread = one 16-byte word: 8 consecutive k of (block nb, chunk c, tap, octet, column nn).
+__device__ __forceinline__ void h1_job(const PnnpPackJob& j, int64_t blk, int nblk) {
+    const float* __restrict__ w = j.src; unsigned short* __restrict__ u = reinterpret_cast<unsigned short*>(j.dst);
+    const int N = j.K, K = j.N;
+    const int K16 = j.Kvalid / 16, NB = (N + 31) / 32;
+    const float s = __uint_as_float((unsigned)(pnnp_h2_scale_exp(j.amax[0]) + 127) << 23);
+    const unsigned words = (unsigned)NB * K16 * 10 * 2 * 32;       // (< 2^31 / 8: the launcher's job_blocks bound)
+    for (unsigned t = (unsigned)blk * 256 + threadIdx.x; t < words; t += (unsigned)nblk * 256) {
+        const unsigned nn = t & 31, oct = (t >> 5) & 1;
+        unsigned r = t >> 6;
+        const unsigned tap = r % 10; r /= 10;
+        const unsigned c = r % (unsigned)K16, nb = r / (unsigned)K16;
+        const int k0 = (int)(c * 16 + oct * 8), n = (int)(nb * 32 + nn);
+        unsigned hw[4];
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            float v[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int k = k0 + e + q;
+                v[q] = (tap < 9 && k < K && n < N) ? w[((int64_t)n * K + k) * 9 + tap] : 0.f;
+            }
+            const _Float16 h0 = (_Float16)(v[0] * s), h1 = (_Float16)(v[1] * s);
+            hw[e >> 1] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+        }
+        reinterpret_cast<uint4*>(u)[t] = make_uint4(hw[0], hw[1], hw[2], hw[3]);      // (destination order IS the enumeration order)
+    }
+}
+
 // max |src[0 .. n)| -> slot (non-negative floats order like their bit patterns; NaN counts as larger than inf: a diverged tensor is flagged)
 __device__ __forceinline__ void amax_job(const PnnpPackJob& j, int64_t blk, int nblk) {
     const float* __restrict__ x = j.src;
@@ -240,11 +273,13 @@ __global__ void __launch_bounds__(256) pack_jobs_kernel(const JobTable tb) {
     else if (job.kind == 4) h2_job(job, (int64_t)blockIdx.x - b0, nblk);
     else if (job.kind == 5) amax_job(job, (int64_t)blockIdx.x - b0, nblk);
     else if (job.kind == 6) h2mat_job(job, (int64_t)blockIdx.x - b0, nblk);
+    else if (job.kind == 7) h1_job(job, (int64_t)blockIdx.x - b0, nblk);
     else gather_job(job, (int64_t)blockIdx.x - b0, nblk);
 }
 
 int job_blocks(const PnnpPackJob& j) {
     if (j.kind == 5) { const int64_t b5 = (j.sk + 256 * 16 - 1) / (256 * 16); return (int)(b5 > 128 ? 128 : (b5 < 1 ? 1 : b5)); }      // (<= 128 atomics per slot)
+    if (j.kind == 7) { const int64_t b7 = ((int64_t)j.Kvalid / 16 * ((j.K + 31) / 32) * 640 + 255) / 256; return (int)(b7 > 2048 ? 2048 : (b7 < 1 ? 1 : b7)); }
     const int64_t total = j.kind == 1 ? (int64_t)j.K * j.N : j.kind == 3 ? (int64_t)((j.K + 7) / 8 * 8) * j.N : j.kind == 6 ? (int64_t)(j.K / 8) * j.N : (j.kind == 2 ? (int64_t)j.Kvalid * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (j.kind == 4 ? (int64_t)j.Kvalid / 8 * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (int64_t)j.T * j.K * j.N));
     int64_t b = (total + 255) / 256;
     const int64_t cap = j.kind == 1 ? 4096 : 2048;
@@ -279,7 +314,7 @@ int pnnp_pack_jobs_f32(const PnnpPackJob* jobs, int n, void* stream) {
         for (int i = 0; i < tb.n; ++i) {
             const PnnpPackJob& j = jobs[i0 + i];
             if (j.kind == 5) { if (!j.src || !j.dst || j.sk < 0) return PNNP_E_INVALID; }
-            else if (!j.src || !j.dst || j.K <= 0 || j.N <= 0 || (j.kind == 4 && (!j.amax || j.Kvalid <= 0 || (j.Kvalid & 15))) || (j.kind == 0 && (j.T <= 0 || (j.K & 3))) || (j.kind == 2 && (j.Kvalid <= 0 || (j.Kvalid & 15))) || ((j.kind == 3 || j.kind == 6) && (j.T <= 0 || j.Ndst <= 0 || (j.K & 7))) || (j.kind == 6 && !j.amax)       /* kind 3 enumerates whole 8-row groups */) return PNNP_E_INVALID;
+            else if (!j.src || !j.dst || j.K <= 0 || j.N <= 0 || ((j.kind == 4 || j.kind == 7) && (!j.amax || j.Kvalid <= 0 || (j.Kvalid & 15))) || (j.kind == 0 && (j.T <= 0 || (j.K & 3))) || (j.kind == 2 && (j.Kvalid <= 0 || (j.Kvalid & 15))) || ((j.kind == 3 || j.kind == 6) && (j.T <= 0 || j.Ndst <= 0 || (j.K & 7))) || (j.kind == 6 && !j.amax)       /* kind 3 enumerates whole 8-row groups */) return PNNP_E_INVALID;
             tb.job[i] = j;
             blocks += job_blocks(j);
             tb.blk_end[i] = blocks;
@@ -360,6 +395,18 @@ int pnnp_pack_jobs_add_h2(PnnpPackJob* jobs, int* n, int cap, const float* w, vo
     }
     return ok ? PNNP_OK : PNNP_E_WORKSPACE;
 }
+// fp16x1 pack of a 3x3 Conv2d weight for the pnnp_conv3x3_h1_* kernels (csrc/conv_h1s.hip): forward orientation only (K = Cin padded to Cin_pad, a multiple
+// of 16; N = Cout padded to 32 inside the pack); size: pnnp_h1_weight_bytes.  `amax`: the weight tensor's slot, as for pnnp_pack_jobs_add_h2.
+int pnnp_pack_jobs_add_h1(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, int Cin_pad, const unsigned* amax) {
+    if (!jobs || !n || !w || !fwd || !amax || Cout <= 0 || Cin <= 0 || Cin_pad < Cin || (Cin_pad & 15) || (((uintptr_t)fwd) & 15)) return PNNP_E_INVALID;
+    // (h1_job indexes 16-byte words with 32 bits)
+    if ((int64_t)(Cin_pad / 16) * ((Cout + 31) / 32) * 640 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+    PnnpPackJob j{};
+    j.src = w; j.dst = reinterpret_cast<float*>(fwd); j.kind = 7; j.K = Cout; j.N = Cin; j.amax = amax; j.Kvalid = Cin_pad;
+    return push(jobs, n, cap, j) ? PNNP_OK : PNNP_E_WORKSPACE;
+}
+// bytes of one h1 pack: per (K rounded up to 16) / 16 chunks and (N rounded up to 32) / 32 column blocks 10 taps x 1024 B (9 hi', 1 zero)
+int64_t pnnp_h1_weight_bytes(int K, int N) { return (int64_t)((K + 15) / 16) * ((N + 31) / 32) * 10240; }
 // max |x[0 .. count)| -> atomicMax into *slot (the caller zeroes the slot first)
 int pnnp_pack_jobs_add_amax(PnnpPackJob* jobs, int* n, int cap, const float* x, int64_t count, unsigned* slot) {
     if (!jobs || !n || !x || !slot || count < 0) return PNNP_E_INVALID;

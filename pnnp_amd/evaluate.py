@@ -14,6 +14,7 @@ rendered to sRGB by the pure-tensor ISP (process.raw2rgb_v2, csrc/isp.hip) and s
 plot_sample(res=None) (utils/visualization.py:55-63).  The rawpy renderer, matplotlib figures, file writing and checkpoint selection
 stay outside (out of scope).  The IMX686 frame 4x1736x2312 takes the padded branch (2312 % 16 = 8 -> 4x1744x2320).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -25,7 +26,40 @@ from ._lib import PnnpError
 from .metrics import IlluminanceCorrect, quality_assess
 
 
-def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, clamp=False):
+@contextlib.contextmanager
+def _precision(net, precision):
+    """``precision=`` of the functions below: None leaves the engine's policy alone; 'fp16' runs the eval forward's stride-1 3x3 layers with ONE fp16
+    piece per operand (ConvPolicy.h1_eval, csrc/conv_h1s.hip), 'fp32' on the float32-accurate default path (fp16x2), for the duration of the call; the
+    engine's previous setting comes back afterwards, also when the call raises.  Changing the switch invalidates the weight packs as set_policy does:
+    alternating precisions per call re-packs each time -- to serve one precision, call ``net.engine.set_policy(h1_eval=True)`` once instead."""
+    if precision is None:
+        yield
+        return
+    if precision not in ('fp32', 'fp16'):
+        raise PnnpError(f"precision must be None, 'fp32' or 'fp16', got {precision!r}")
+    eng = getattr(net, 'engine', None)
+    if eng is None or not hasattr(eng, 'set_policy'):
+        if precision == 'fp16':
+            raise PnnpError("precision='fp16' needs a network with a HIP engine")
+        yield
+        return
+    want, prev = precision == 'fp16', bool(eng.policy.h1_eval)
+    if want and not eng.policy.h2:
+        raise PnnpError("precision='fp16' needs the fp16x2 family (set_policy(h2=True)): its amax slots are what the scale is made of")
+    if want == prev:
+        yield
+        return
+    had = 'h1_eval' in eng._h2_sub
+    eng.set_policy(h1_eval=want)
+    try:
+        yield
+    finally:
+        eng.set_policy(h1_eval=prev)
+        if not had:
+            eng._h2_sub.pop('h1_eval', None)
+
+
+def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, clamp=False, precision=None):
     """The network over one frame in overlapping tiles (the reference's eval_crop -> net per tile -> eval_merge, syn_datasets.py:109-159,
     trainer_SID.py:209-218,351-357): CUDA [1,C,h,w] -> [1,out_nc,h,w].  The frame need not be a multiple of 16 and may be larger than
     what one forward takes (engine.effective_policy); ``patch_size`` must be a multiple of 16 and ``h, w >= patch_size - base``.
@@ -39,7 +73,15 @@ def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, 
     and about the same for ResUnet.  A last chunk of another size gets a buffer set of its own.  The result does not depend on the
     chunking beyond what the kernels' own choices by batch size (plan.py) change: float32 rounding.
 
-    A ``net`` without a HIP engine runs as ``eval_merge(net(eval_crop(frame)))``, chunked the same way."""
+    A ``net`` without a HIP engine runs as ``eval_merge(net(eval_crop(frame)))``, chunked the same way.
+
+    ``precision``: None / 'fp32' / 'fp16' for this call (``_precision``: 'fp16' = one fp16 rounding per operand in the stride-1 3x3 layers, float32
+    accumulation; the switch is restored afterwards, and alternating precisions per call re-packs the weights each time)."""
+    with _precision(net, precision):
+        return _forward_tiled(net, frame, patch_size, base, tile_batch, ratio, clamp)
+
+
+def _forward_tiled(net, frame, patch_size, base, tile_batch, ratio, clamp):
     from . import ops
     from .tiles import TileGrid, _frame
     x = _frame(frame, 'forward_tiled')
@@ -64,21 +106,22 @@ def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, 
     return out
 
 
-def predict(net, raw, wp, bl, patch_size, base=64, bias=None, tile_batch=None):
+def predict(net, raw, wp, bl, patch_size, base=64, bias=None, tile_batch=None, precision=None):
     """The reference's ``predict`` (trainer_SID.py:345-360, trainer_LRID.py:341-356): a Bayer frame [H,W] (uint16 / float32, numpy or CUDA)
     -> the denoised packed frame, a DEVICE tensor [C, H/2, W/2] (the reference saves it as .npy; writing files stays with the caller).
     The mosaic is packed by the raw2bayer kernel with the camera's ``wp`` / ``bl`` (the reference calls raw2bayer(raw + bl) with that
-    function's defaults 1023 / 64), then ``forward_tiled`` without ratio or clamp."""
+    function's defaults 1023 / 64), then ``forward_tiled`` without ratio or clamp (``precision``: as there)."""
     from . import isp_ops
     if not torch.is_tensor(raw):
         raw = torch.from_numpy(np.ascontiguousarray(raw))
     if raw.dim() != 2:
         raise PnnpError(f'predict expects one Bayer frame [H,W], got {tuple(raw.shape)}')
     packed = isp_ops.raw2bayer(raw.cuda(), wp=wp, bl=bl, norm=True, clip=False, bias=np.zeros(4) if bias is None else bias)
-    return forward_tiled(net, packed[None], patch_size, base=base, tile_batch=tile_batch)[0]
+    return forward_tiled(net, packed[None], patch_size, base=base, tile_batch=tile_batch, precision=precision)[0]
 
 
-def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None, tiles=None):
+def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None, tiles=None,
+             precision=None):
     """-> dict(dn=<clamped (and corrected) prediction>, lr=<clamped input>, metrics=<device tensor [PSNR_dn, SSIM_dn, PSNR_lr, SSIM_lr]>).
 
     ``imgs_lr``, ``imgs_hr``: CUDA [1,C,H,W] (the eval loaders use batch_size 1); ``ratio``: scalar / [1] tensor, needed when
@@ -92,7 +135,15 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
     ``tiles=dict(patch_size=, base=64, tile_batch=None)``: the network runs over the frame in overlapping tiles (``forward_tiled``; the
     reference's strategy for frames that do not fit, trainer_SID.py:209-218) instead of in one forward: the reflect-pad-4 branch is not
     taken, the frame need not be a multiple of 16, and ``x ratio`` and the clamp of the prediction ride on the merge.  Everything behind
-    that is the same; without ``tiles`` nothing changes."""
+    that is the same; without ``tiles`` nothing changes.
+
+    ``precision``: None / 'fp32' / 'fp16' for the network forward of this call, as in ``forward_tiled``; the engine's previous setting is restored
+    afterwards, also when the call raises."""
+    with _precision(net, precision):
+        return _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles)
+
+
+def _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles):
     if not imgs_lr.is_cuda or not imgs_hr.is_cuda:
         raise PnnpError('evaluate needs CUDA tensors (pnnp_amd has no CPU path)')
     if imgs_lr.dim() != 4 or imgs_lr.shape[0] != 1:
@@ -108,7 +159,8 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
                 raise PnnpError('ori=True needs the ratio (trainer_SID.py:231-233)')
             r_dev = ratio.reshape(-1)[:1].float().contiguous() if (ori and torch.is_tensor(ratio) and ratio.is_cuda) else None
             r = 1.0 if (not ori or r_dev is not None) else float(torch.as_tensor(ratio).reshape(-1)[0])
-            dn = forward_tiled(net, lr_in, ratio=r_dev if r_dev is not None else r, clamp=True, **tiles)
+            dn = _forward_tiled(net, lr_in, ratio=r_dev if r_dev is not None else r, clamp=True,
+                                **{'base': 64, 'tile_batch': None, **tiles})
             if dn.shape != lr_in.shape:
                 raise PnnpError(f'evaluate: the network returns {tuple(dn.shape)} for a {tuple(lr_in.shape)} frame')
             # the clamped (x ratio) input frame: the tail kernel on the frame itself, its second output not asked for
@@ -183,9 +235,10 @@ class EvalLoop:
     """Accumulates what `SID_Trainer.eval` reports over a dataset: `metrics` (name -> [PSNR, SSIM], the content of
     metrics.pkl) and the log line of trainer_SID.py:309-312."""
 
-    def __init__(self, net, ori=False, brightness_correct=True, tiles=None):
-        """``tiles``: as in ``evaluate`` (every frame of the dataset runs in overlapping tiles); None: whole frames"""
-        self.net, self.ori, self.brightness_correct, self.tiles = net, ori, brightness_correct, tiles
+    def __init__(self, net, ori=False, brightness_correct=True, tiles=None, precision=None):
+        """``tiles``: as in ``evaluate`` (every frame of the dataset runs in overlapping tiles); None: whole frames.  ``precision``: as in ``evaluate``,
+        for every step (the switch is set and restored per step: with another precision than the engine's own, set it on the engine once instead)"""
+        self.net, self.ori, self.brightness_correct, self.tiles, self.precision = net, ori, brightness_correct, tiles, precision
         self.corrector = IlluminanceCorrect()
         self.reset()
 
@@ -200,7 +253,7 @@ class EvalLoop:
 
     def step(self, name, imgs_lr, imgs_hr, ratio=None, epoch=-1, render=None):
         out = evaluate(self.net, imgs_lr, imgs_hr, ratio=ratio, ori=self.ori, brightness_correct=self.brightness_correct,
-                       epoch=epoch, corrector=self.corrector, render=render, tiles=self.tiles)
+                       epoch=epoch, corrector=self.corrector, render=render, tiles=self.tiles, precision=self.precision)
         self._pending.append((name, out['metrics']))          # device tensors: one host sync per dataset, in finish()
         if render is not None:
             self._pending_rgb.append(out['metrics_rgb'])

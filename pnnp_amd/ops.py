@@ -52,6 +52,7 @@ def _prep():
         L.pnnp_x3g_wgrad_workspace_floats.restype = C.c_int64
         L.pnnp_x3mat_bytes.restype = C.c_int64
         L.pnnp_h2_weight_bytes.restype = C.c_int64
+        L.pnnp_h1_weight_bytes.restype = C.c_int64
         L.pnnp_h2_bits_words.restype = C.c_int64
         L.pnnp_h2mat_bytes.restype = C.c_int64
         L.pnnp_h2g_wgrad_workspace_floats.restype = C.c_int64
@@ -141,6 +142,16 @@ class PackJobs:
         check(_prep().pnnp_pack_jobs_add_h2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci,
                                             cin_pad or (ci + 15) // 16 * 16, ptr(slot)), 'pack_jobs_add_h2')
         self.keep += [w, fwd, dgrad]
+        return slot
+
+    def add_h1(self, w, dst, cin_pad=None):
+        """The fp16x1 forward pack (csrc/conv_h1s.hip) of a 3x3 Conv2d weight; dst: a uint8 buffer of h1_weight_bytes.  Returns the weight tensor's
+        amax slot (what the kernels take as ``amax_w``)."""
+        co, ci = w.shape[0], w.shape[1]
+        slot = self.weight_slot(w)
+        check(_prep().pnnp_pack_jobs_add_h1(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(dst), co, ci, cin_pad or (ci + 15) // 16 * 16, ptr(slot)),
+              'pack_jobs_add_h1')
+        self.keep += [w, dst]
         return slot
 
     def add_h2_convt(self, w, fwd, dgrad):
@@ -494,6 +505,58 @@ def conv_h2_fwd_pool(x1, x2, w_h2, amax_w, bias, y, pooled, codes, cout, act, am
                 sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):      # (+ the pooled map and its one-byte codes)
         check(_prep().pnnp_conv3x3_h2_fwd_pool_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y),
                                                    ptr(pooled), ptr(codes), ptr(amax_y), ptr(bits_y), B, H, W, cout, act, stream()), 'conv_h2_fwd_pool')
+    return y
+
+
+# ---- the fp16x1 ("h1") family: csrc/conv_h1s.hip -- the h2 forward entries with one fp16 piece per operand, eval forward only (no sign bits)
+def h1_supported(K, N):
+    return bool(_prep().pnnp_h1_supported(int(K), int(N)))
+
+
+def h1_weight_bytes(K, N):
+    return int(_prep().pnnp_h1_weight_bytes(int(K), int(N)))
+
+
+def conv_h1_fwd(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, amax_x2=None, amax_y=None, residual=None):
+    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
+        check(_prep().pnnp_conv3x3_h1_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(residual),
+                                              ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_h1_fwd')
+    return y
+
+
+def conv_h1_fwd_splitk(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, ksplit, ws, amax_x2=None, amax_y=None):
+    """conv_h1_fwd with K cut into ``ksplit`` slices (h2_splitk): partial sums into ``ws`` (>= ksplit * y.numel() floats), one fixed-order reduce."""
+    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1, ws)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub='splitk'):
+        check(_prep().pnnp_conv3x3_h1_fwd_splitk_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
+                                                     B, H, W, cout, act, int(ksplit), ptr(ws), _i64(ws.numel()), stream()), 'conv_h1_fwd_splitk')
+    return y
+
+
+def conv_h1_fwd_head(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, head_w, head_b, out, amax_x2=None, amax_y=None, residual=None):
+    """conv_h1_fwd + the network's 1x1 head in one kernel: ``out`` NCHW [B,4,H,W] (+ ``residual``, NCHW); ``y`` None: the 32-channel map is not stored."""
+    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1, head_w, out, residual)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9 + 2.0 * B * H * W * cout * 4, 4.0 * B * H * W * (C1 + C2 + (cout if y is not None else 0) + 4), sub='bn32'):
+        check(_prep().pnnp_conv3x3_h1_fwd_head_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
+                                                   ptr(head_w), ptr(head_b), ptr(residual), ptr(out), B, H, W, cout, act, stream()), 'conv_h1_fwd_head')
+    return out
+
+
+def conv_h1_fwd_pool(x1, x2, w_h1, amax_w, bias, y, pooled, codes, cout, act, amax_x1, amax_x2=None, amax_y=None):
+    require_cuda(x1, x2, w_h1, y, pooled, codes, amax_w, amax_x1)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + 1.25 * cout) + B * H * W * cout / 4,
+                sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):
+        check(_prep().pnnp_conv3x3_h1_fwd_pool_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y),
+                                                   ptr(pooled), ptr(codes), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_h1_fwd_pool')
     return y
 
 

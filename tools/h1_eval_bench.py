@@ -1,0 +1,176 @@
+"""The opt-in fp16x1 eval forward (ConvPolicy.h1_eval, csrc/conv_h1s.hip) against the default fp16x2 one: time and accuracy.
+
+    python tools/h1_eval_bench.py [--out profiles/r7/h1_eval.txt] [--reps 5]
+
+Everything runs in ONE process.  Two networks with the same weights, one with the switch on and one with it off (so that no weight
+re-pack falls into a timed region), are called alternately -- h2 h1 h2 h1 ... -- inside every round, after warm-up rounds; device
+events around back-to-back eval forwards only.  Per call: median [min .. max] over the rounds; a ratio is quoted beside the spread of
+its baseline, and the baseline of every ratio is the fp16x2 path measured in this same run.
+
+Workloads (those of tools/tiled_eval_bench.py / profiles/r7/tiled_eval.txt): UNetSeeInDark nf = 32 on one 4x512x512 crop, on 16 crops, on
+the whole 4x1424x2128 SID frame and through forward_tiled (20 tiles of 512); ResUnet nf = 32 on the 16-crop batch.  A per-layer split of
+the 3x3 launches (the wrappers' own device events, pnnp_amd.ops.PROFILE) says which levels gain.
+
+Accuracy: a synthetic SID-like frame (rand^2.2 * 0.1 with 0.1 % saturated pixels, as tests/test_gpu_soak.py builds its crops) + noise
+through variance-preserving random weights: PSNR of the fp16x1 output against a float64 forward of the same weights (tests/_h1_ref.py,
+on a 512 x 512 crop) and against the fp16x2 output (whole frame), and what `evaluate` reports for both precisions."""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, 'tests'))
+import numpy as np
+import torch
+
+from oracle import net_torch as O
+from pnnp_amd import ops
+from pnnp_amd.archs import ResUnet, UNetSeeInDark
+from pnnp_amd.evaluate import evaluate, forward_tiled
+
+H, W, P, BASE = 1424, 2128, 512, 64
+
+
+def timed(fn, inner):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(inner):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / inner            # us per call
+
+
+def rounds(forms, reps, inner, warm=2):
+    out = {k: [] for k in forms}
+    for r in range(warm + reps):
+        for k, fn in forms.items():
+            t = timed(fn, inner)
+            if r >= warm:
+                out[k].append(t)
+    return out
+
+
+def stat(v):
+    return f'{np.median(v):10.1f} us [{min(v):.1f} .. {max(v):.1f}]'
+
+
+def make(arch, res=False):
+    shapes = O.unet_param_shapes(nf=32) if arch == 'unet' else O.resunet_param_shapes(nf=32)
+    sd = O.init_state_he(shapes, seed=5, res_scale=0.5, head_scale=0.05, head_bias=0.1)
+    nets = []
+    for h1 in (False, True):
+        net = (UNetSeeInDark if arch == 'unet' else ResUnet)(dict(nframes=1, res=res, nf=32, in_nc=4, out_nc=4))
+        net.load_state_dict({k: v.clone() for k, v in sd.items()})
+        net = net.cuda().eval()
+        net.engine.set_policy(h1_eval=h1)
+        nets.append(net)
+    return nets[0], nets[1], sd
+
+
+def sid_like(shape, gen):
+    hr = torch.rand(*shape, device='cuda', generator=gen) ** 2.2 * 0.1
+    sat = torch.rand(*shape, device='cuda', generator=gen) < 1e-3
+    return torch.where(sat, torch.ones_like(hr), hr)
+
+
+def psnr(a, b):
+    return float(-10.0 * torch.log10(((a.double() - b.double()) ** 2).mean()))
+
+
+def per_layer(net, x, names, reps=5):
+    """{layer: median us} of the 3x3 launches of one eval forward, in launch order (ops.PROFILE: events around every wrapper call)"""
+    acc = {n: [] for n in names}
+    for _ in range(reps + 1):
+        ops.PROFILE = []
+        with torch.no_grad():
+            net.engine.forward(x, False)
+        torch.cuda.synchronize()
+        recs = [r for r in ops.PROFILE if r[0] in ('conv9_fwd_h1', 'conv9_fwd_h2')]
+        ops.PROFILE = None
+        assert len(recs) == len(names), (len(recs), len(names))
+        for n, r in zip(names, recs):
+            acc[n].append(r[3].elapsed_time(r[4]) * 1e3)
+    return {n: float(np.median(v[1:])) for n, v in acc.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r7', 'h1_eval.txt'))
+    ap.add_argument('--reps', type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('h1_eval_bench needs the GPU: nothing here is measured without one')
+    g = torch.Generator(device='cuda').manual_seed(1)
+    u2, u1, sd_u = make('unet')
+    r2, r1, _ = make('resunet')
+    hr = sid_like((1, 4, H, W), g)
+    frame = (hr + 0.02 * torch.randn(1, 4, H, W, device='cuda', generator=g)).clamp(0, 1)
+    crop1 = frame[:, :, 400:912, 800:1312].contiguous()
+    crops16 = torch.cat([frame[:, :, 64 * i:64 * i + 512, 100 * i:100 * i + 512] for i in range(14)] + [crop1, crop1.flip(-1)]).contiguous()
+    L = [f'fp16x1 (h1_eval) against fp16x2 eval forwards on {torch.cuda.get_device_name(0)}; nf = 32; random variance-preserving weights',
+         f'per call, median [min .. max] over {a.reps} rounds, h2 and h1 alternated inside every round (two engines, same weights: no re-pack is timed); device events', '']
+
+    def fwd(net, x):
+        def f():
+            with torch.no_grad():
+                net.engine.forward(x, False)
+        return f
+    work = [('UNet, 1 crop 4x512x512', fwd(u2, crop1), fwd(u1, crop1), 20),
+            ('UNet, 16 crops 4x512x512', fwd(u2, crops16), fwd(u1, crops16), 4),
+            (f'UNet, whole frame 4x{H}x{W}', fwd(u2, frame), fwd(u1, frame), 4),
+            ('UNet, forward_tiled, 20 tiles of 512', lambda: forward_tiled(u2, frame, P, BASE), lambda: forward_tiled(u1, frame, P, BASE), 3),
+            ('ResUnet, 16 crops 4x512x512', fwd(r2, crops16), fwd(r1, crops16), 4)]
+    L.append('(a) eval forward, fp16x2 (the default) and fp16x1')
+    for name, f2, f1, inner in work:
+        res = rounds({'h2': f2, 'h1': f1}, a.reps, inner)
+        m2, m1 = np.median(res['h2']), np.median(res['h1'])
+        spread = 100 * (max(res['h2']) - min(res['h2'])) / m2
+        L.append(f'  {name}')
+        L.append(f'    fp16x2 {stat(res["h2"])}')
+        L.append(f'    fp16x1 {stat(res["h1"])}   fp16x2 / fp16x1 = {m2 / m1:.3f} x  (spread of the fp16x2 rounds: {spread:.1f} % of their median)')
+    L.append('')
+
+    names = [f'conv{i}_{j}' for i in range(1, 10) for j in (1, 2)]
+    for label, x in (('16 crops 4x512x512', crops16), (f'whole frame 4x{H}x{W}', frame)):
+        t2, t1 = per_layer(u2, x, names), per_layer(u1, x, names)
+        plan = u1.engine._plan
+        L.append(f'(b) UNet, {label}: the 3x3 launches one by one (events around every launch: sums exceed (a)); level = 1 full resolution .. 5')
+        L.append('    layer     level  launch          fp16x2 us   fp16x1 us   ratio')
+        lv2, lv1 = {}, {}
+        for n in names:
+            i = int(n[4])
+            lvl = i if i <= 5 else 10 - i
+            lv2[lvl] = lv2.get(lvl, 0.0) + t2[n]; lv1[lvl] = lv1.get(lvl, 0.0) + t1[n]
+            L.append(f'    {n:9s} {lvl:5d}  {plan[n].fwd:12s} {t2[n]:11.1f} {t1[n]:11.1f} {t2[n] / t1[n]:7.2f}')
+        for lvl in sorted(lv2):
+            L.append(f'    level {lvl}: fp16x2 {lv2[lvl]:9.1f} us, fp16x1 {lv1[lvl]:9.1f} us, ratio {lv2[lvl] / lv1[lvl]:.2f}')
+        L.append(f'    all 3x3 launches: fp16x2 {sum(t2.values()):.1f} us, fp16x1 {sum(t1.values()):.1f} us, ratio {sum(t2.values()) / sum(t1.values()):.2f}')
+        L.append('')
+
+    # ---- accuracy
+    from _h1_ref import h1_unet_forward
+    with torch.no_grad():
+        y2, y1 = u2(crop1).clone(), u1(crop1).clone()
+        f2, f1 = u2(frame).clone(), u1(frame).clone()
+    sd64 = {k: v.double().cuda() for k, v in sd_u.items()}
+    exact = h1_unet_forward(sd64, crop1)
+    rel = lambda p, q: float((p.double() - q.double()).norm() / q.double().norm())
+    L.append('(c) accuracy, UNet on the synthetic SID-like frame (outputs in [0, 1] units; PSNR = -10 log10 MSE)')
+    L.append(f'  512 x 512 crop against the float64 forward of the same weights: fp16x1 PSNR {psnr(y1, exact):.1f} dB (relative L2 {rel(y1, exact):.2e}), '
+             f'fp16x2 PSNR {psnr(y2, exact):.1f} dB (relative L2 {rel(y2, exact):.2e})')
+    L.append(f'  whole frame, fp16x1 against fp16x2: PSNR {psnr(f1, f2):.1f} dB, relative L2 {rel(f1, f2):.2e}, max |difference| {float((f1 - f2).abs().max()):.2e} (max |output| {float(f2.abs().max()):.2e})')
+    m2 = evaluate(u2, frame, hr)['metrics'].cpu().tolist()
+    m1 = evaluate(u1, frame, hr)['metrics'].cpu().tolist()
+    L.append(f'  evaluate(frame, target) with untrained weights: fp16x2 PSNR {m2[0]:.4f} dB SSIM {m2[1]:.6f}; fp16x1 PSNR {m1[0]:.4f} dB SSIM {m1[1]:.6f}; '
+             f'change {m1[0] - m2[0]:+.4f} dB, {m1[1] - m2[1]:+.6f}')
+    text = '\n'.join(L) + '\n'
+    print(text)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
+if __name__ == '__main__':
+    main()
