@@ -347,6 +347,26 @@ int pnnp_conv1x1_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, co
 int pnnp_conv1x1_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, int mode1, int accum1, unsigned* amax_dx1 /*or null*/,
                                  float* dx2 /*or null*/, int C2, const float* mask2, int mode2, int accum2, int B, int H, int W, void* stream);
+/* ---- the fp16x1 ("h1") pointwise layers: the three FORWARD entries above with ONE scaled fp16 piece per float32 operand (csrc/gemm_s.h on the scheme of
+ * csrc/gemm_h1s.hip): one matrix instruction per 32 channels and 16 x 16 block where fp16x2 issues three; error as for pnnp_conv3x3_h1_fwd_f32 (one fp16 rounding
+ * per operand, float32 accumulation).  EVAL FORWARD ONLY and opt-in (ConvPolicy.h1_pointwise): no backward entries; the launcher answers PNNP_E_UNSUPPORTED to
+ * masks, bit images, accumulating or second destinations.  Argument lists, amax contract and tile set of the _h2_ twins; shapes: pnnp_h1_pointwise_supported
+ * (= pnnp_gemm_h2_supported: K % 32 == 0, N % 32 == 0).  Weights: kind-8 packs of pnnp_h1_pointwise_weight_bytes(K, N) = 2 K N bytes with the forward GEMM's
+ * K and N (ConvTranspose2d: Cin, 4 Cout; 1x1: C1 + C2, Cout; stride 2: 9 Cin, Cout) -- the kind-6 layout [N/32][K/32][octet 4][32][8] fp16 without its lo'
+ * plane, hi' = f16(w 2^se) with the weight tensor's amax slot; zero-fill the buffer first, as for the h2 packs.  Every tensor pointer 16-byte aligned, slots
+ * 4-byte: PNNP_E_INVALID otherwise. */
+int pnnp_h1_pointwise_supported(int K, int N);
+int64_t pnnp_h1_pointwise_weight_bytes(int K, int N);
+int pnnp_pack_jobs_add_h1_convt(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cin, int Cout, const unsigned* amax);
+int pnnp_pack_jobs_add_h1_1x1(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, const unsigned* amax);
+int pnnp_pack_jobs_add_h1_s2(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, const unsigned* amax);
+int pnnp_convt_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias /*or null*/, float* y,
+                          unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, void* stream);
+int pnnp_conv1x1_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                            const unsigned* amax_w, const float* bias /*or null*/, const float* residual /*or null*/, float* y, unsigned* amax_y /*or null*/,
+                            int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv_s2_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias /*or null*/, float* y,
+                            unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
 /* pointwise layers on the bf16 matrix cores (csrc/gemm_x3.hip): ConvTranspose2d k2 s2 (archs/Unet.py:35-47), Conv2d 1x1 (ResidualBlock
  * shortcuts, archs/modules.py:176-197), Conv2d 3x3 stride 2 (archs/modules.py:130-138); same contracts as pnnp_convt2x2_* /
  * pnnp_conv_fwd_f32 + pnnp_conv_bwd_data_f32 with taps = 1 / pnnp_conv3x3s2_*; channel counts in multiples of 32; the weights are

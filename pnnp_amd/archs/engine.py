@@ -60,7 +60,7 @@ class _EngineBase:
         if policy is None:
             cur = dict(wino=self.policy.wino, wino_wgrad=self.policy.wino_wgrad, wino_mink=self.policy.wino_mink, x3=self.policy.x3,
                        thin=self.policy.thin, pool_fused=self.policy.pool_fused, h2=self.policy.h2)
-            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
+            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval', 'h1_pointwise'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
                 if k in kw:
                     self._h2_sub[k] = bool(kw.pop(k))
             if 'unpool_levels' in kw:                              # which encoder levels unpool_fused applies to (plan.py)
@@ -222,6 +222,11 @@ class _EngineBase:
             kind, cip, cop = self._layer(name)
             b = lambda sfx, n, dt=u8: self._buf(name + sfx, n, dev, dt)
             co, ci = (w.shape[1], w.shape[0]) if kind == 'convt' else (w.shape[0], w.shape[1])
+            if kind != '3x3' and pf == 'h1':           # (eval plans under h1_pointwise) the one-piece forward pack of a pointwise layer; no backward-data pack exists
+                fkn = (9 * ci, co) if kind == 's2' else (ci, 4 * co) if kind == 'convt' else (ci, co)
+                f = b(':h1mf', ops.h1_pointwise_weight_bytes(*fkn))
+                self._wp[name] = (f, None, getattr(jobs, f'add_h1_{kind}')(w, f))
+                continue
             if kind != '3x3' and pf in ('h2', 'x3'):   # 3x3 stride 2, ConvTranspose2d 2x2 stride 2, 1x1: the pointwise fp16x2 / bf16x3 GEMM kernels
                 mat = ops.h2mat_bytes if pf == 'h2' else ops.x3mat_bytes
                 if kind == 's2':                       # (K, N) of the forward GEMM, of the backward-data GEMM, and how many of those
@@ -511,6 +516,8 @@ class _EngineBase:
         fam = plan[name].fwd
         if fam == 'h2':
             ops.conv_s2_h2_fwd(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
+        elif fam == 'h1':                                    # (eval only, ConvPolicy.h1_pointwise) the fp16x1 twin
+            ops.conv_s2_h1_fwd(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
         elif fam == 'x3':
             ops.conv_s2_x3_fwd(x, f, bias, y, cout, amax_y=T.slot(name) if plan.h2 else None)
         else:
@@ -544,6 +551,8 @@ class _EngineBase:
         fam = plan[name].fwd
         if fam == 'h2':
             ops.conv1x1_h2_fwd(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
+        elif fam == 'h1':
+            ops.conv1x1_h1_fwd(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
         elif fam == 'x3':
             ops.conv1x1_x3_fwd(x1, x2, f, bias, y, cout, act)
         else:
@@ -570,6 +579,8 @@ class _EngineBase:
         fam = plan[name].fwd
         if fam == 'h2':
             ops.convt_h2_fwd(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
+        elif fam == 'h1':
+            ops.convt_h1_fwd(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
         elif fam == 'x3':
             ops.convt_x3_fwd(x, f, bias, y, cout, amax_y=T.slot(name) if plan.h2 else None)
         else:

@@ -7,7 +7,9 @@ its own forward.  Families: 'h2' (fp16x2), 'x3' (bf16x3), 'wino' (Winograd), 'di
 4-channel ends); a forward may carry a fused variant ('h2+pool', 'x3+pool', 'h2+splitk', 'h2+head'; conv10_1 is then 'fused'), and
 ResUnet's identity-shortcut backward-data 'FAMILY+res'.  None: the pass does not run (eval, or no gradient w.r.t. the input).
 'h1' (fp16x1, csrc/conv_h1s.hip) exists in EVAL plans only, under ``ConvPolicy.h1_eval``: the stride-1 3x3 layers whose forward would
-be 'h2' / 'h2+pool' / 'h2+splitk' / 'h2+head' take the same variant of 'h1'; everything else in the plan stays as it is."""
+be 'h2' / 'h2+pool' / 'h2+splitk' / 'h2+head' take the same variant of 'h1'; everything else in the plan stays as it is -- unless
+``ConvPolicy.h1_pointwise`` is on as well: then the ConvTranspose2d / 1x1 / stride-2 steps whose forward is 'h2' become 'h1' too
+(csrc/gemm_h1s.hip)."""
 import os
 
 from .. import ops
@@ -46,13 +48,16 @@ class ConvPolicy:
         # one rounding per operand, float32 accumulation, ~1e-3 of the activations' scale; 5 matrix instructions per chunk where fp16x2 issues 14).  Only
         # meaningful with ``h2``; a training plan ignores it.  Not part of key(): the packs are keyed by the plan's pack families ('h1')
         self.h1_eval = bool(h2) and os.environ.get('PNNP_H1_EVAL', '0') != '0'
+        # (opt-in, off by default) ... and, with ``h1_eval``, the ConvTranspose2d / 1x1 / stride-2 layers that are on the pointwise fp16x2 kernel as well
+        # (csrc/gemm_h1s.hip: one matrix instruction per 32 channels where fp16x2 issues three).  Without ``h2`` and ``h1_eval`` it changes nothing.
+        self.h1_pointwise = bool(h2) and os.environ.get('PNNP_H1_POINTWISE', '0') != '0'
 
     def key(self):
         return (self.wino, self.wino_wgrad, self.wino_mink, self.x3, self.thin, self.pool_fused, self.h2, self.h2_wgrad, self.h2_pointwise, self.head_fused, self.splitk, self.convt_bits)
 
     def plan_key(self):
         """What a cached Plan depends on: key() (the families and packs) + the switches that only change the launch sequence."""
-        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval)
+        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval, self.h1_pointwise)
 
     def use_thin_head(self, cin, cout, npix):
         return self.thin and ops.head_supported(cin, cout, npix)
@@ -148,6 +153,19 @@ class Plan:
         self.packs = tuple(s.pack for s in self.steps.values())
         return self
 
+    # (kind, K, N) of a pointwise forward GEMM that stays on fp16x2 under h1_pointwise because one piece measured SLOWER there (none so far)
+    H1_POINTWISE_KEEP_H2 = frozenset()
+
+    def to_h1_pointwise(self, layers):
+        """(eval plans, ConvPolicy.h1_eval and h1_pointwise) ``layers``: name -> (kind, K, N) of the ConvTranspose2d / 1x1 / stride-2 steps' forward GEMMs; those
+        whose forward is the pointwise fp16x2 launch take the fp16x1 kernel, pack family 'h1'.  ``h2`` stays as it was (the amax slots are still kept up)."""
+        for n, knd in layers.items():
+            s = self.steps[n]
+            if s.fwd == 'h2' and s.pack[0] == 'h2' and knd not in self.H1_POINTWISE_KEEP_H2 and ops.h1_pointwise_supported(knd[1], knd[2]):
+                s.fwd, s.pack = 'h1', ('h1', s.pack[1])
+        self.packs = tuple(s.pack for s in self.steps.values())
+        return self
+
 
 def _pad8(c):
     return (c + 7) // 8 * 8
@@ -226,6 +244,8 @@ def resolve_unet(ch, cin, cout, pol, train, B, H, W):
         st['conv9_2'].fwd, st['conv9_2'].ks, st['conv10_1'].fwd = 'h2+head', 1, 'fused'
     if not train and pol.h1_eval and pol.h2:
         plan.to_h1([f'conv{i}_{j}' for i in range(1, 10) for j in (1, 2)])
+        if pol.h1_pointwise:
+            plan.to_h1_pointwise({f'upv{i}': ('convt', ch[10 - i], 4 * ch[9 - i]) for i in range(6, 10)})
     if train:
         for i in range(6, 10):             # the skip gradient of conv{i}_1 + MaxPool2d backward in one epilogue: needs the skip tensor's sign bits and codes
             skip = st[f'conv{10 - i}_2']
@@ -288,6 +308,11 @@ def resolve_resunet(ch, cin, cout, pol, train, B, H, W):
     if not train:
         if pol.h1_eval and pol.h2:
             plan.to_h1(['conv_in'] + [f'b{i}_{j}' for i in range(1, 10) for j in (0, 1)])
+            if pol.h1_pointwise:
+                pw = {f'upv{i}': ('convt', ch[10 - i], 4 * ch[9 - i]) for i in range(6, 10)}
+                pw.update({f'sc{i}': ('1x1', ch[9 - i], ch[9 - i]) for i in range(6, 10)})          # (K per segment of cat([up, skip]))
+                pw.update({f'pool{i}': ('s2', ch[i - 1], ch[i]) for i in range(1, 5)})             # (K per tap segment)
+                plan.to_h1_pointwise(pw)
         return plan
     for l in range(1, 6):
         st[f'b{l}_0'].dgrad += '+res'                  # identity shortcut: d/d(input) = dgrad(block) + g in one kernel

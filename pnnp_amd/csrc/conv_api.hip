@@ -8,6 +8,7 @@ int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);  
 int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);        // csrc/gemm_x3.hip (one tap per K segment, bf16x3 split)
 int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg);                        // its argument validation alone
 int pnnp_gemm_h2s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h2s.hip (the same GEMMs on the fp16x2 scheme; both: the kernel of csrc/gemm_s.h)
+int pnnp_gemm_h1s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h1s.hip (... on the fp16x1 scheme: eval forward only)
 
 namespace {
 
@@ -587,6 +588,49 @@ int pnnp_conv3x3s2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* ama
         slice += ns;
     }
     return PNNP_OK;
+}
+
+// ---------------------------------------------------------------- the same FORWARD layers with ONE fp16 piece per operand (fp16x1, csrc/gemm_h1s.hip)
+// Eval forward only: the argument lists of the _h2_ forward entries above; weights: the kind-8 packs of pnnp_pack_jobs_add_h1_convt / _1x1 / _s2.
+int pnnp_h1_pointwise_supported(int K, int N) { return pnnp_gemm_h2_supported(K, N); }
+namespace {
+int gemm_h1_go(H2Args& h, int chan_per_seg, hipStream_t st) {
+    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg);
+    if (rc != PNNP_OK) return rc;
+    if (!pnnp_h1_pointwise_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
+    h.g.seg_channels = chan_per_seg;
+    h.g.chunks_per_seg = chan_per_seg / 32;                         // 32-channel items, as fp16x2
+    if ((int64_t)(h.g.Ntot / 32) * h.g.nseg * h.g.chunks_per_seg * 2048 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+    return pnnp_gemm_h1s_launch(h, st);
+}
+}  // namespace
+int pnnp_convt_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y,
+                          unsigned* amax_y, int B, int H, int W, int Cout, void* stream) {
+    if (!x || !w_h1 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    convt_fwd_args(h.g, x, Cin, w_h1, bias, y, B, H, W, Cout);
+    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
+    return gemm_h1_go(h, Cin, as_stream(stream));
+}
+int pnnp_conv1x1_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1,
+                            const unsigned* amax_w, const float* bias, const float* residual, float* y, unsigned* amax_y,
+                            int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w_h1 || !y || !amax_x1 || !amax_w || (x2 && !amax_x2) || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    fwd_args(h.g, x1, C1, x2, C2, w_h1, bias, residual, y, B, H, W, Cout, act);
+    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x1; h.amax_in[1] = x2 ? amax_x2 : nullptr; h.amax_w = amax_w;
+    return gemm_h1_go(h, C1, as_stream(stream));
+}
+int pnnp_conv_s2_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y,
+                            unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x || !w_h1 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    s2_fwd_args(h.g, x, Cin, w_h1, bias, y, B, H, W, Cout, act);
+    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
+    return gemm_h1_go(h, Cin, as_stream(stream));
 }
 
 // ConvTranspose2d(Cin, Cout, 2, stride=2) forward   archs/Unet.py:35-47

@@ -23,7 +23,7 @@ namespace {
 struct H2s {
     using Args = H2Args;
     static __host__ __device__ const IgemmArgs& g(const H2Args& h) { return h.g; }
-    static constexpr int CH = 32, PIECES = 2, NAF = 3;
+    static constexpr int CH = 32, PIECES = 2, NAF = 3, NPROD = 3;
     static constexpr bool SCALED = true, BITS = true;
     static constexpr bool gen_lean(int, int) { return true; }
     static constexpr int nwm(int, int) { return 4; }                 // always 256 pixels

@@ -1,7 +1,8 @@
 // Pointwise convolutions as a float32 GEMM on the low-precision matrix cores, float32 operands split into pieces on the fly: ConvTranspose2d(k2, s2)
 // forward / backward-data, 1x1 shortcuts, the stride-2 3x3 convolution as 9 strided taps and its backward-data per input-pixel parity class -- one tap
-// per K segment, described by IgemmArgs (csrc/gemm_x3.hip's contract).  ONE kernel for both split schemes; what a scheme is comes from the `Scheme` of
-// csrc/gemm_x3s.hip (bf16x3, exact three-way split) or csrc/gemm_h2s.hip (fp16x2, two scaled pieces), which also pick the tile of a launch.
+// per K segment, described by IgemmArgs (csrc/gemm_x3.hip's contract).  ONE kernel for all split schemes; what a scheme is comes from the `Scheme` of
+// csrc/gemm_x3s.hip (bf16x3, exact three-way split), csrc/gemm_h2s.hip (fp16x2, two scaled pieces) or csrc/gemm_h1s.hip (fp16x1, one scaled piece: eval forward
+// only), which also pick the tile of a launch.
 //
 // A workgroup has SPECIALISED waves:
 //   8 CONSUMER waves (two per SIMD), 64 pixels x WN = 64 (32) columns each: ds_read_b128 + v_mfma_f32_16x16x32 only (pieces concatenated along K, weights
@@ -15,9 +16,9 @@
 //
 // A Scheme provides: Args (the kernel argument) and g() (its IgemmArgs part); CH channels per K item and PIECES per value (images [PIECES][CH / 8][pixel], WBLK1 =
 // PIECES x CH / 8 x 512 bytes); nwm(BN, WN) consumer waves along the pixels (tile = 64 nwm pixels; the others of the 8 only keep the barriers) and lookahead(PT) = A;
-// split() of two values into their pieces (the producers); gen_lean(BN, WN): the general epilogue on a register diet (see there); the consumers' NAF pixel-operand forms and three weight-operand forms as the coefficients AH, AC / WH, WC, WO
+// split() of two values into their pieces (the producers); gen_lean(BN, WN): the general epilogue on a register diet (see there); the consumers' NAF pixel-operand forms and NPROD (three, or fp16x1's one) weight-operand forms as the coefficients AH, AC / WH, WC, WO
 // of the image plane [piece][octet] / the row [32][16 B] of a weight block that a K group of a form reads (see the consumers' offsets),
-// fa(sp) / fb(sp) = the forms of product sp of the three per (pixel block, column block), and mfma(); SCALED / scale_exps(): power-of-two operand scales
+// fa(sp) / fb(sp) = the forms of product sp of the NPROD per (pixel block, column block), and mfma(); SCALED / scale_exps(): power-of-two operand scales
 // from the tensors' amax slots, undone in the epilogue; BITS: whether Args carries sign-bit masks (EK_BWDB).
 #pragma once
 #include "igemm.h"
@@ -267,7 +268,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
         }
     }
     const int wn = wave % Cfg::NWN, wm = wave / Cfg::NWN;             // this wave's column group / pixel-row pair
-    constexpr int MB = 2 * MT, NAF = Scheme::NAF;
+    constexpr int MB = 2 * MT, NAF = Scheme::NAF, NPR = Scheme::NPROD;      // pixel-operand forms; products (= weight-operand forms) per (pixel block, column block)
     f32x4 acc[MB][NB];
 #pragma unroll
     for (int i = 0; i < MB; ++i)
@@ -280,30 +281,31 @@ gemm_s_kernel(const typename Scheme::Args ha) {
     const int pb = wm * (MT * 32) + r16;
 #define GS_AOFF(f) (((Scheme::AH[f] == 2 ? (q16 & 2) : (q16 >> 1) * Scheme::AH[f]) + Scheme::AC[f] + (q16 & 1)) * PT + pb)
 #define GS_BOFF(f) ((((Scheme::WH[f] == 2 ? (q16 & 2) : (q16 >> 1) * Scheme::WH[f]) + Scheme::WC[f] + (q16 & 1) * Scheme::WO) * 32 + r16) * 16)
-    const int aoff0 = GS_AOFF(0), aoff1 = GS_AOFF(1), aoff2 = GS_AOFF(NAF - 1);
-    const int boff0 = GS_BOFF(0), boff1 = GS_BOFF(1), boff2 = GS_BOFF(2);
+    // (a scheme with fewer forms repeats its last one: the unused offsets fold away)
+    const int aoff0 = GS_AOFF(0), aoff1 = GS_AOFF(NAF > 1 ? 1 : 0), aoff2 = GS_AOFF(NAF - 1);
+    const int boff0 = GS_BOFF(0), boff1 = GS_BOFF(NPR > 1 ? 1 : 0), boff2 = GS_BOFF(NPR - 1);
 #undef GS_AOFF
 #undef GS_BOFF
     auto mfma_item = [&](int st, int img) {
         const char* wst = wsb + st * Cfg::WS_STAGE + wn * NTW * WBLK1;
         const u32x4* xim = xs + img * XS_F4;
-        u32x4 Av[MB][NAF], Bv[2][3];
+        u32x4 Av[MB][NAF], Bv[2][NPR];
         auto a_read = [&](int mb, int f) { Av[mb][f] = xim[(f == 0 ? aoff0 : (f == 1 ? aoff1 : aoff2)) + (mb >> 1) * 32 + 16 * (mb & 1)]; };
         auto b_read = [&](int j, int f, int buf) {
             Bv[buf][f] = *reinterpret_cast<const u32x4*>(wst + (j >> 1) * WBLK1 + (f == 0 ? boff0 : (f == 1 ? boff1 : boff2)) + (j & 1) * 256);
         };
 #pragma unroll
-        for (int f = 0; f < 3; ++f) b_read(0, 2 - f, 0);
+        for (int f = 0; f < NPR; ++f) b_read(0, NPR - 1 - f, 0);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
             for (int f = NAF - 1; f >= 0; --f) a_read(mb, f);
         __builtin_amdgcn_sched_barrier(0);
-        static_for<0, NB * MB * 3>([&](auto Gc) {
+        static_for<0, NB * MB * NPR>([&](auto Gc) {
             constexpr int gi = decltype(Gc)::value;
-            constexpr int j = gi / (MB * 3), w = gi % (MB * 3), mb = w / 3, sp = w % 3, buf = j & 1;
+            constexpr int j = gi / (MB * NPR), w = gi % (MB * NPR), mb = w / NPR, sp = w % NPR, buf = j & 1;
             acc[mb][j] = Scheme::mfma(Bv[buf][Scheme::fb(sp)], Av[mb][Scheme::fa(sp)], acc[mb][j]);      // smallest terms first
-            if constexpr (w < 3 && j + 1 < NB) b_read(j + 1, 2 - w, buf ^ 1);
+            if constexpr (w < NPR && j + 1 < NB) b_read(j + 1, NPR - 1 - w, buf ^ 1);
             __builtin_amdgcn_sched_barrier(0);
         });
     };

@@ -21,7 +21,7 @@ namespace {
 struct X3s {
     using Args = IgemmArgs;
     static __host__ __device__ const IgemmArgs& g(const IgemmArgs& a) { return a; }
-    static constexpr int CH = 16, PIECES = 3, NAF = 2;
+    static constexpr int CH = 16, PIECES = 3, NAF = 2, NPROD = 3;
     static constexpr bool SCALED = false, BITS = false;
     static constexpr bool gen_lean(int BN, int WN) { return BN == 64 && WN == 32; }      // (csrc/gemm_s.h: slower on the wide tiles, an occupancy step on this one)
     static constexpr int nwm(int BN, int WN) { return NCW / (BN / WN); }      // every consumer wave computes: 512 pixels where a wave takes the tile's whole width

@@ -10,6 +10,7 @@
 //               that a kind-5 job of an EARLIER launch filled)
 //   job kind 5: max |src| -> atomicMax into a 4-byte slot (csrc/h2.h)
 //   job kind 7: 3x3 filters scaled like kind 4 and rounded to ONE fp16 piece for csrc/conv_h1s.hip (forward orientation only)
+//   job kind 8: a strided K x N matrix scaled like kind 6 and rounded to ONE fp16 piece for csrc/gemm_h1s.hip (forward orientation only)
 // The builders below produce exactly the jobs the per-layer entry points used to launch (same formulas, same layouts).
 #include "common.h"
 #include "h2.h"
@@ -163,6 +164,28 @@ __device__ __forceinline__ void h2mat_job(const PnnpPackJob& j, int64_t blk, int
     }
 }
 
+// fp16x1 pack of a K x N weight matrix for csrc/gemm_s.h on the scheme of csrc/gemm_h1s.hip:  dst (fp16) [Ntot/32][K32tot][octet 4][32][8]  (2048 bytes per 32-channel
+//   item and 32-column block): the kind-6 layout keeping the hi' plane and dropping lo'; sub-matrix addressing and scale exactly as h2mat_job, hi' = f16(W s).
+__device__ __forceinline__ void h1mat_job(const PnnpPackJob& j, int64_t blk, int nblk) {
+    const float* __restrict__ w = j.src; unsigned short* __restrict__ u = reinterpret_cast<unsigned short*>(j.dst);
+    const int K = j.K, N = j.N, K32 = j.T, k_off = (int)j.st;
+    const float s = __uint_as_float((unsigned)(pnnp_h2_scale_exp(j.amax[0]) + 127) << 23);
+    const unsigned total = (unsigned)(K / 8) * (unsigned)N;          // one thread = 8 consecutive k of one column: one 16-byte word (K % 8 == 0)
+    for (unsigned t = (unsigned)blk * 256 + threadIdx.x; t < total; t += (unsigned)nblk * 256) {
+        const unsigned n = t % (unsigned)N, k0 = (t / (unsigned)N) * 8;
+        const float* src = w + j.off + (int64_t)k0 * j.sk + (int64_t)n * j.sn;
+        unsigned hw[4];
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            const _Float16 h0 = (_Float16)(src[(int64_t)e * j.sk] * s), h1 = (_Float16)(src[(int64_t)(e + 1) * j.sk] * s);
+            hw[e >> 1] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+        }
+        const int kk = k_off + (int)k0, nn = j.n_off + (int)n;
+        unsigned short* o = u + ((int64_t)(nn >> 5) * K32 + (kk >> 5)) * 1024 + ((kk >> 3) & 3) * 256 + (nn & 31) * 8;
+        *reinterpret_cast<uint4*>(o) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+    }
+}
+
 // fp16x2 pack of a 3x3 Conv2d weight for csrc/conv_h2s.hip:  dst (fp16) [N/32][K16] x { hi' [tap 9][octet 2][32][8], lo' [tap 10][octet 2][32][8] }
 //   (the tenth lo' tap is ZERO: the partner of the unpaired ninth tap; 19456 bytes per 32-column block and chunk)
 //   element (k, n, tap) as in x3_job;  W s with s = 2^pnnp_h2_scale_exp(*amax) (amax >= max |w|: a kind-5 job), hi' = f16(W s), lo' = f16(W s - hi')
@@ -274,13 +297,14 @@ __global__ void __launch_bounds__(256) pack_jobs_kernel(const JobTable tb) {
     else if (job.kind == 5) amax_job(job, (int64_t)blockIdx.x - b0, nblk);
     else if (job.kind == 6) h2mat_job(job, (int64_t)blockIdx.x - b0, nblk);
     else if (job.kind == 7) h1_job(job, (int64_t)blockIdx.x - b0, nblk);
+    else if (job.kind == 8) h1mat_job(job, (int64_t)blockIdx.x - b0, nblk);
     else gather_job(job, (int64_t)blockIdx.x - b0, nblk);
 }
 
 int job_blocks(const PnnpPackJob& j) {
     if (j.kind == 5) { const int64_t b5 = (j.sk + 256 * 16 - 1) / (256 * 16); return (int)(b5 > 128 ? 128 : (b5 < 1 ? 1 : b5)); }      // (<= 128 atomics per slot)
     if (j.kind == 7) { const int64_t b7 = ((int64_t)j.Kvalid / 16 * ((j.K + 31) / 32) * 640 + 255) / 256; return (int)(b7 > 2048 ? 2048 : (b7 < 1 ? 1 : b7)); }
-    const int64_t total = j.kind == 1 ? (int64_t)j.K * j.N : j.kind == 3 ? (int64_t)((j.K + 7) / 8 * 8) * j.N : j.kind == 6 ? (int64_t)(j.K / 8) * j.N : (j.kind == 2 ? (int64_t)j.Kvalid * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (j.kind == 4 ? (int64_t)j.Kvalid / 8 * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (int64_t)j.T * j.K * j.N));
+    const int64_t total = j.kind == 1 ? (int64_t)j.K * j.N : j.kind == 3 ? (int64_t)((j.K + 7) / 8 * 8) * j.N : (j.kind == 6 || j.kind == 8) ? (int64_t)(j.K / 8) * j.N : (j.kind == 2 ? (int64_t)j.Kvalid * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (j.kind == 4 ? (int64_t)j.Kvalid / 8 * (((j.T ? j.N : j.K) + 31) / 32 * 32) * 9 : (int64_t)j.T * j.K * j.N));
     int64_t b = (total + 255) / 256;
     const int64_t cap = j.kind == 1 ? 4096 : 2048;
     return (int)(b > cap ? cap : (b < 1 ? 1 : b));
@@ -314,7 +338,7 @@ int pnnp_pack_jobs_f32(const PnnpPackJob* jobs, int n, void* stream) {
         for (int i = 0; i < tb.n; ++i) {
             const PnnpPackJob& j = jobs[i0 + i];
             if (j.kind == 5) { if (!j.src || !j.dst || j.sk < 0) return PNNP_E_INVALID; }
-            else if (!j.src || !j.dst || j.K <= 0 || j.N <= 0 || ((j.kind == 4 || j.kind == 7) && (!j.amax || j.Kvalid <= 0 || (j.Kvalid & 15))) || (j.kind == 0 && (j.T <= 0 || (j.K & 3))) || (j.kind == 2 && (j.Kvalid <= 0 || (j.Kvalid & 15))) || ((j.kind == 3 || j.kind == 6) && (j.T <= 0 || j.Ndst <= 0 || (j.K & 7))) || (j.kind == 6 && !j.amax)       /* kind 3 enumerates whole 8-row groups */) return PNNP_E_INVALID;
+            else if (!j.src || !j.dst || j.K <= 0 || j.N <= 0 || ((j.kind == 4 || j.kind == 7) && (!j.amax || j.Kvalid <= 0 || (j.Kvalid & 15))) || (j.kind == 0 && (j.T <= 0 || (j.K & 3))) || (j.kind == 2 && (j.Kvalid <= 0 || (j.Kvalid & 15))) || ((j.kind == 3 || j.kind == 6 || j.kind == 8) && (j.T <= 0 || j.Ndst <= 0 || (j.K & 7))) || ((j.kind == 6 || j.kind == 8) && !j.amax)       /* kind 3 enumerates whole 8-row groups */) return PNNP_E_INVALID;
             tb.job[i] = j;
             blocks += job_blocks(j);
             tb.blk_end[i] = blocks;
@@ -503,6 +527,31 @@ int pnnp_pack_jobs_add_h2_s2(PnnpPackJob* jobs, int* n, int cap, const float* w,
     return ok ? PNNP_OK : PNNP_E_WORKSPACE;
 }
 int64_t pnnp_h2mat_bytes(int K, int N) { return (int64_t)K * N * 4; }
+// fp16x1 packs for csrc/gemm_h1s.hip (eval forward only: no backward-data orientation): the forward sub-matrix jobs of the add_h2_* builders above in the
+// kind-8 layout (the kind-6 layout without its lo' plane: 2 bytes per weight), scaled with the weight tensor's amax slot.  Size: pnnp_h1_pointwise_weight_bytes(K, N)
+// with the forward GEMM's K and N (ConvTranspose2d: Cin, 4 Cout; 1x1: Cin, Cout; stride 2: 9 Cin, Cout).  Channel counts in multiples of 32, fwd 16-byte aligned.
+int pnnp_pack_jobs_add_h1_convt(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cin, int Cout, const unsigned* amax) {
+    if (!jobs || !n || !w || !fwd || !amax || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || (((uintptr_t)fwd) & 15)) return PNNP_E_INVALID;
+    const int n0 = *n;
+    const int rc = pnnp_pack_jobs_add_h2_convt(jobs, n, cap, w, fwd, nullptr, Cin, Cout, amax);
+    for (int i = n0; i < *n; ++i) jobs[i].kind = 8;
+    return rc;
+}
+int pnnp_pack_jobs_add_h1_1x1(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, const unsigned* amax) {
+    if (!jobs || !n || !w || !fwd || !amax || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || (((uintptr_t)fwd) & 15)) return PNNP_E_INVALID;
+    const int n0 = *n;
+    const int rc = pnnp_pack_jobs_add_h2_1x1(jobs, n, cap, w, fwd, nullptr, Cout, Cin, amax);
+    for (int i = n0; i < *n; ++i) jobs[i].kind = 8;
+    return rc;
+}
+int pnnp_pack_jobs_add_h1_s2(PnnpPackJob* jobs, int* n, int cap, const float* w, void* fwd, int Cout, int Cin, const unsigned* amax) {
+    if (!jobs || !n || !w || !fwd || !amax || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || (((uintptr_t)fwd) & 15)) return PNNP_E_INVALID;
+    const int n0 = *n;
+    const int rc = pnnp_pack_jobs_add_h2_s2(jobs, n, cap, w, fwd, nullptr, Cout, Cin, amax);
+    for (int i = n0; i < *n; ++i) jobs[i].kind = 8;
+    return rc;
+}
+int64_t pnnp_h1_pointwise_weight_bytes(int K, int N) { return (int64_t)K * N * 2; }
 
 
 // bytes of one x3 pack: K (reduction channels, rounded up to 16) x N (channels written, rounded up to 32) x 9 taps x 3 pieces x 2 B

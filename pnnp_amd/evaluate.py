@@ -31,17 +31,36 @@ def _precision(net, precision):
     """``precision=`` of the functions below: None leaves the engine's policy alone; 'fp16' runs the eval forward's stride-1 3x3 layers with ONE fp16
     piece per operand (ConvPolicy.h1_eval, csrc/conv_h1s.hip), 'fp32' on the float32-accurate default path (fp16x2), for the duration of the call; the
     engine's previous setting comes back afterwards, also when the call raises.  Changing the switch invalidates the weight packs as set_policy does:
-    alternating precisions per call re-packs each time -- to serve one precision, call ``net.engine.set_policy(h1_eval=True)`` once instead."""
+    alternating precisions per call re-packs each time -- to serve one precision, call ``net.engine.set_policy(h1_eval=True)`` once instead.
+    'fp16_all' is 'fp16' with the ConvTranspose2d / 1x1 / stride-2 layers on one fp16 piece as well (ConvPolicy.h1_pointwise, csrc/gemm_h1s.hip): both
+    switches are set for the call and both come back."""
     if precision is None:
         yield
         return
-    if precision not in ('fp32', 'fp16'):
-        raise PnnpError(f"precision must be None, 'fp32' or 'fp16', got {precision!r}")
+    if precision not in ('fp32', 'fp16', 'fp16_all'):
+        raise PnnpError(f"precision must be None, 'fp32', 'fp16' or 'fp16_all', got {precision!r}")
     eng = getattr(net, 'engine', None)
     if eng is None or not hasattr(eng, 'set_policy'):
-        if precision == 'fp16':
-            raise PnnpError("precision='fp16' needs a network with a HIP engine")
+        if precision != 'fp32':
+            raise PnnpError(f"precision='{precision}' needs a network with a HIP engine")
         yield
+        return
+    if precision == 'fp16_all':
+        if not eng.policy.h2:
+            raise PnnpError("precision='fp16_all' needs the fp16x2 family (set_policy(h2=True)): its amax slots are what the scale is made of")
+        prev = {k: bool(getattr(eng.policy, k)) for k in ('h1_eval', 'h1_pointwise')}
+        if all(prev.values()):
+            yield
+            return
+        had = {k: k in eng._h2_sub for k in prev}
+        eng.set_policy(h1_eval=True, h1_pointwise=True)
+        try:
+            yield
+        finally:
+            eng.set_policy(**prev)
+            for k, h in had.items():
+                if not h:
+                    eng._h2_sub.pop(k, None)
         return
     want, prev = precision == 'fp16', bool(eng.policy.h1_eval)
     if want and not eng.policy.h2:
@@ -75,8 +94,8 @@ def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, 
 
     A ``net`` without a HIP engine runs as ``eval_merge(net(eval_crop(frame)))``, chunked the same way.
 
-    ``precision``: None / 'fp32' / 'fp16' for this call (``_precision``: 'fp16' = one fp16 rounding per operand in the stride-1 3x3 layers, float32
-    accumulation; the switch is restored afterwards, and alternating precisions per call re-packs the weights each time)."""
+    ``precision``: None / 'fp32' / 'fp16' / 'fp16_all' for this call (``_precision``: 'fp16' = one fp16 rounding per operand in the stride-1 3x3 layers, float32
+    accumulation, 'fp16_all' = in the ConvTranspose2d / 1x1 / stride-2 layers as well; the switch is restored afterwards, and alternating precisions per call re-packs the weights each time)."""
     with _precision(net, precision):
         return _forward_tiled(net, frame, patch_size, base, tile_batch, ratio, clamp)
 
@@ -137,7 +156,7 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
     taken, the frame need not be a multiple of 16, and ``x ratio`` and the clamp of the prediction ride on the merge.  Everything behind
     that is the same; without ``tiles`` nothing changes.
 
-    ``precision``: None / 'fp32' / 'fp16' for the network forward of this call, as in ``forward_tiled``; the engine's previous setting is restored
+    ``precision``: None / 'fp32' / 'fp16' / 'fp16_all' for the network forward of this call, as in ``forward_tiled``; the engine's previous setting is restored
     afterwards, also when the call raises."""
     with _precision(net, precision):
         return _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles)

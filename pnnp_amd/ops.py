@@ -53,6 +53,7 @@ def _prep():
         L.pnnp_x3mat_bytes.restype = C.c_int64
         L.pnnp_h2_weight_bytes.restype = C.c_int64
         L.pnnp_h1_weight_bytes.restype = C.c_int64
+        L.pnnp_h1_pointwise_weight_bytes.restype = C.c_int64
         L.pnnp_h2_bits_words.restype = C.c_int64
         L.pnnp_h2mat_bytes.restype = C.c_int64
         L.pnnp_h2g_wgrad_workspace_floats.restype = C.c_int64
@@ -175,6 +176,31 @@ class PackJobs:
         slot = self.weight_slot(w)
         check(_prep().pnnp_pack_jobs_add_h2_s2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci, ptr(slot)), 'pack_jobs_add_h2_s2')
         self.keep += [w, fwd, dgrad]
+        return slot
+
+    def add_h1_convt(self, w, fwd):
+        """The fp16x1 forward pack (csrc/gemm_h1s.hip) of a ConvTranspose2d(2, 2) weight; fwd: a zero-filled uint8 buffer of
+        h1_pointwise_weight_bytes(Cin, 4 Cout).  Returns the weight tensor's amax slot."""
+        ci, co = w.shape[0], w.shape[1]
+        slot = self.weight_slot(w)
+        check(_prep().pnnp_pack_jobs_add_h1_convt(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ci, co, ptr(slot)), 'pack_jobs_add_h1_convt')
+        self.keep += [w, fwd]
+        return slot
+
+    def add_h1_1x1(self, w, fwd):
+        """... of a 1x1 Conv2d weight; fwd: h1_pointwise_weight_bytes(Cin, Cout) bytes."""
+        co, ci = w.shape[0], w.shape[1]
+        slot = self.weight_slot(w)
+        check(_prep().pnnp_pack_jobs_add_h1_1x1(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), co, ci, ptr(slot)), 'pack_jobs_add_h1_1x1')
+        self.keep += [w, fwd]
+        return slot
+
+    def add_h1_s2(self, w, fwd):
+        """... of a stride-2 3x3 Conv2d weight; fwd: h1_pointwise_weight_bytes(9 Cin, Cout) bytes."""
+        co, ci = w.shape[0], w.shape[1]
+        slot = self.weight_slot(w)
+        check(_prep().pnnp_pack_jobs_add_h1_s2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), co, ci, ptr(slot)), 'pack_jobs_add_h1_s2')
+        self.keep += [w, fwd]
         return slot
 
     def add_x3_convt(self, w, fwd, dgrad):
@@ -682,6 +708,42 @@ def conv_s2_h2_bwd_data(g, amax_g, w_h2_s2dgrad, amax_w, dx, mask=None, mode=0, 
     with _Timed('conv9s2_dgrad_h2', 2.0 * B * (H // 2) * (W // 2) * g.shape[3] * Cin * 9):
         check(_prep().pnnp_conv3x3s2_h2_bwd_data_f32(ptr(g), g.shape[3], ptr(amax_g), ptr(w_h2_s2dgrad), ptr(amax_w), ptr(dx), Cin, ptr(mask), mode, int(accum), ptr(amax_dx),
                                                      B, H, W, stream()), 'conv_s2_h2_bwd_data')
+
+
+# ---- the fp16x1 ("h1") pointwise forwards: csrc/gemm_h1s.hip -- the three h2 forward entries above with one fp16 piece per operand, eval forward only
+def h1_pointwise_supported(K, N):
+    return bool(_prep().pnnp_h1_pointwise_supported(int(K), int(N)))
+
+
+def h1_pointwise_weight_bytes(K, N):
+    """Bytes of a kind-8 pack; K, N of the forward GEMM (ConvTranspose2d: Cin, 4 Cout; 1x1: Cin, Cout; stride 2: 9 Cin, Cout)."""
+    return int(_prep().pnnp_h1_pointwise_weight_bytes(int(K), int(N)))
+
+
+def convt_h1_fwd(x, amax_x, w_h1, amax_w, bias, y, cout, amax_y=None):
+    require_cuda(x, w_h1, y, amax_x, amax_w)
+    B, H, W, Cin = x.shape
+    with _Timed('convt_fwd_h1', 8.0 * B * H * W * Cin * cout, 4.0 * B * H * W * (Cin + 4 * cout)):
+        check(_prep().pnnp_convt_h1_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, stream()), 'convt_h1_fwd')
+    return y
+
+
+def conv1x1_h1_fwd(x1, amax_x1, x2, amax_x2, w_h1, amax_w, bias, y, cout, act, residual=None, amax_y=None):
+    require_cuda(x1, x2, w_h1, y, amax_x1, amax_w)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv1_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2), 4.0 * B * H * W * (C1 + C2 + cout)):
+        check(_prep().pnnp_conv1x1_h1_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(residual), ptr(y), ptr(amax_y),
+                                              B, H, W, cout, act, stream()), 'conv1x1_h1_fwd')
+    return y
+
+
+def conv_s2_h1_fwd(x, amax_x, w_h1, amax_w, bias, y, cout, act, amax_y=None):
+    require_cuda(x, w_h1, y, amax_x, amax_w)
+    B, H, W, Cin = x.shape
+    with _Timed('conv9s2_fwd_h1', 2.0 * B * (H // 2) * (W // 2) * cout * Cin * 9):
+        check(_prep().pnnp_conv_s2_h1_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_s2_h1_fwd')
+    return y
 
 
 def conv1x1_x3_fwd(x1, x2, w_x3, bias, y, cout, act, residual=None):

@@ -1,15 +1,17 @@
-"""The opt-in fp16x1 eval forward (ConvPolicy.h1_eval, csrc/conv_h1s.hip) against the default fp16x2 one: time and accuracy.
+"""The opt-in fp16x1 eval forwards -- 'fp16' (ConvPolicy.h1_eval, csrc/conv_h1s.hip: the stride-1 3x3 layers) and 'fp16_all' (+ h1_pointwise,
+csrc/gemm_h1s.hip: ConvTranspose2d, 1x1 and stride-2 layers as well) -- against the default fp16x2 one: time and accuracy.
 
-    python tools/h1_eval_bench.py [--out profiles/r7/h1_eval.txt] [--reps 5]
+    python tools/h1_eval_bench.py [--out profiles/r7/h1_pointwise.txt] [--reps 5]
 
-Everything runs in ONE process.  Two networks with the same weights, one with the switch on and one with it off (so that no weight
-re-pack falls into a timed region), are called alternately -- h2 h1 h2 h1 ... -- inside every round, after warm-up rounds; device
+Everything runs in ONE process.  Three networks with the same weights, one per mode (so that no weight
+re-pack falls into a timed region), are called alternately -- h2 h1 all h2 h1 all ... -- inside every round, after warm-up rounds; device
 events around back-to-back eval forwards only.  Per call: median [min .. max] over the rounds; a ratio is quoted beside the spread of
 its baseline, and the baseline of every ratio is the fp16x2 path measured in this same run.
 
 Workloads (those of tools/tiled_eval_bench.py / profiles/r7/tiled_eval.txt): UNetSeeInDark nf = 32 on one 4x512x512 crop, on 16 crops, on
 the whole 4x1424x2128 SID frame and through forward_tiled (20 tiles of 512); ResUnet nf = 32 on the 16-crop batch.  A per-layer split of
-the 3x3 launches (the wrappers' own device events, pnnp_amd.ops.PROFILE) says which levels gain.
+the 3x3 launches (the wrappers' own device events, pnnp_amd.ops.PROFILE) says which levels gain, and one of the pointwise launches
+which of those gain from one piece (the yardstick of the 'fp16_all' column is the 'fp16' column of the same run).
 
 Accuracy: a synthetic SID-like frame (rand^2.2 * 0.1 with 0.1 % saturated pixels, as tests/test_gpu_soak.py builds its crops) + noise
 through variance-preserving random weights: PSNR of the fp16x1 output against a float64 forward of the same weights (tests/_h1_ref.py,
@@ -60,13 +62,13 @@ def make(arch, res=False):
     shapes = O.unet_param_shapes(nf=32) if arch == 'unet' else O.resunet_param_shapes(nf=32)
     sd = O.init_state_he(shapes, seed=5, res_scale=0.5, head_scale=0.05, head_bias=0.1)
     nets = []
-    for h1 in (False, True):
+    for h1, pw in ((False, False), (True, False), (True, True)):
         net = (UNetSeeInDark if arch == 'unet' else ResUnet)(dict(nframes=1, res=res, nf=32, in_nc=4, out_nc=4))
         net.load_state_dict({k: v.clone() for k, v in sd.items()})
         net = net.cuda().eval()
-        net.engine.set_policy(h1_eval=h1)
+        net.engine.set_policy(h1_eval=h1, h1_pointwise=pw)
         nets.append(net)
-    return nets[0], nets[1], sd
+    return nets[0], nets[1], nets[2], sd
 
 
 def sid_like(shape, gen):
@@ -79,15 +81,19 @@ def psnr(a, b):
     return float(-10.0 * torch.log10(((a.double() - b.double()) ** 2).mean()))
 
 
-def per_layer(net, x, names, reps=5):
-    """{layer: median us} of the 3x3 launches of one eval forward, in launch order (ops.PROFILE: events around every wrapper call)"""
+CONV3 = ('conv9_fwd_h1', 'conv9_fwd_h2')
+POINTWISE = tuple(f'{k}_fwd_{f}' for k in ('convt', 'conv1', 'conv9s2') for f in ('h1', 'h2'))
+
+
+def per_layer(net, x, names, reps=5, kinds=CONV3):
+    """{layer: median us} of the launches of ``kinds`` of one eval forward, in launch order (ops.PROFILE: events around every wrapper call)"""
     acc = {n: [] for n in names}
     for _ in range(reps + 1):
         ops.PROFILE = []
         with torch.no_grad():
             net.engine.forward(x, False)
         torch.cuda.synchronize()
-        recs = [r for r in ops.PROFILE if r[0] in ('conv9_fwd_h1', 'conv9_fwd_h2')]
+        recs = [r for r in ops.PROFILE if r[0] in kinds]
         ops.PROFILE = None
         assert len(recs) == len(names), (len(recs), len(names))
         for n, r in zip(names, recs):
@@ -97,39 +103,43 @@ def per_layer(net, x, names, reps=5):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r7', 'h1_eval.txt'))
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r7', 'h1_pointwise.txt'))
     ap.add_argument('--reps', type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('h1_eval_bench needs the GPU: nothing here is measured without one')
     g = torch.Generator(device='cuda').manual_seed(1)
-    u2, u1, sd_u = make('unet')
-    r2, r1, _ = make('resunet')
+    u2, u1, ua, sd_u = make('unet')
+    r2, r1, ra, _ = make('resunet')
     hr = sid_like((1, 4, H, W), g)
     frame = (hr + 0.02 * torch.randn(1, 4, H, W, device='cuda', generator=g)).clamp(0, 1)
     crop1 = frame[:, :, 400:912, 800:1312].contiguous()
     crops16 = torch.cat([frame[:, :, 64 * i:64 * i + 512, 100 * i:100 * i + 512] for i in range(14)] + [crop1, crop1.flip(-1)]).contiguous()
-    L = [f'fp16x1 (h1_eval) against fp16x2 eval forwards on {torch.cuda.get_device_name(0)}; nf = 32; random variance-preserving weights',
-         f'per call, median [min .. max] over {a.reps} rounds, h2 and h1 alternated inside every round (two engines, same weights: no re-pack is timed); device events', '']
+    L = [f"fp16x1 eval forwards -- 'fp16' (h1_eval: the stride-1 3x3 layers) and 'fp16_all' (+ h1_pointwise: ConvTranspose2d / 1x1 / stride-2 too) -- against fp16x2 "
+         f'on {torch.cuda.get_device_name(0)}; nf = 32; random variance-preserving weights',
+         f'per call, median [min .. max] over {a.reps} rounds, the three modes alternated inside every round (three engines, same weights: no re-pack is timed); device events', '']
 
     def fwd(net, x):
         def f():
             with torch.no_grad():
                 net.engine.forward(x, False)
         return f
-    work = [('UNet, 1 crop 4x512x512', fwd(u2, crop1), fwd(u1, crop1), 20),
-            ('UNet, 16 crops 4x512x512', fwd(u2, crops16), fwd(u1, crops16), 4),
-            (f'UNet, whole frame 4x{H}x{W}', fwd(u2, frame), fwd(u1, frame), 4),
-            ('UNet, forward_tiled, 20 tiles of 512', lambda: forward_tiled(u2, frame, P, BASE), lambda: forward_tiled(u1, frame, P, BASE), 3),
-            ('ResUnet, 16 crops 4x512x512', fwd(r2, crops16), fwd(r1, crops16), 4)]
-    L.append('(a) eval forward, fp16x2 (the default) and fp16x1')
-    for name, f2, f1, inner in work:
-        res = rounds({'h2': f2, 'h1': f1}, a.reps, inner)
-        m2, m1 = np.median(res['h2']), np.median(res['h1'])
+    work = [('UNet, 1 crop 4x512x512', fwd(u2, crop1), fwd(u1, crop1), fwd(ua, crop1), 20),
+            ('UNet, 16 crops 4x512x512', fwd(u2, crops16), fwd(u1, crops16), fwd(ua, crops16), 4),
+            (f'UNet, whole frame 4x{H}x{W}', fwd(u2, frame), fwd(u1, frame), fwd(ua, frame), 4),
+            ('UNet, forward_tiled, 20 tiles of 512', lambda: forward_tiled(u2, frame, P, BASE), lambda: forward_tiled(u1, frame, P, BASE),
+             lambda: forward_tiled(ua, frame, P, BASE), 3),
+            ('ResUnet, 16 crops 4x512x512', fwd(r2, crops16), fwd(r1, crops16), fwd(ra, crops16), 4)]
+    L.append("(a) eval forward: fp16x2 ('fp32', the default), fp16x1 on the 3x3 layers ('fp16') and on every layer that has a one-piece kernel ('fp16_all')")
+    for name, f2, f1, fa, inner in work:
+        res = rounds({'h2': f2, 'h1': f1, 'all': fa}, a.reps, inner)
+        m2, m1, ma = np.median(res['h2']), np.median(res['h1']), np.median(res['all'])
         spread = 100 * (max(res['h2']) - min(res['h2'])) / m2
+        spread1 = 100 * (max(res['h1']) - min(res['h1'])) / m1
         L.append(f'  {name}')
-        L.append(f'    fp16x2 {stat(res["h2"])}')
-        L.append(f'    fp16x1 {stat(res["h1"])}   fp16x2 / fp16x1 = {m2 / m1:.3f} x  (spread of the fp16x2 rounds: {spread:.1f} % of their median)')
+        L.append(f'    fp32     {stat(res["h2"])}')
+        L.append(f'    fp16     {stat(res["h1"])}   fp32 / fp16 = {m2 / m1:.3f} x  (spread of the fp32 rounds: {spread:.1f} % of their median)')
+        L.append(f'    fp16_all {stat(res["all"])}   fp16 / fp16_all = {m1 / ma:.3f} x, fp32 / fp16_all = {m2 / ma:.3f} x  (spread of the fp16 rounds: {spread1:.1f} %)')
     L.append('')
 
     names = [f'conv{i}_{j}' for i in range(1, 10) for j in (1, 2)]
@@ -149,11 +159,25 @@ def main():
         L.append(f'    all 3x3 launches: fp16x2 {sum(t2.values()):.1f} us, fp16x1 {sum(t1.values()):.1f} us, ratio {sum(t2.values()) / sum(t1.values()):.2f}')
         L.append('')
 
+    # ---- the pointwise launches one by one: fp16x2 (what 'fp16' runs them on: the yardstick) against fp16x1
+    upv = [f'upv{i}' for i in range(6, 10)]
+    res_names = [f'pool{i}' for i in range(1, 5)] + [n for i in range(6, 10) for n in (f'upv{i}', f'sc{i}')]
+    for label, n1, na, x, names in (('UNet, 16 crops 4x512x512', u1, ua, crops16, upv), (f'UNet, whole frame 4x{H}x{W}', u1, ua, frame, upv),
+                                    ('ResUnet, 16 crops 4x512x512', r1, ra, crops16, res_names)):
+        t1, ta = per_layer(n1, x, names, kinds=POINTWISE), per_layer(na, x, names, kinds=POINTWISE)
+        plan = na.engine._plan
+        L.append(f"(d) {label}: the pointwise launches one by one, 'fp16' (fp16x2 kernel) against 'fp16_all' (fp16x1 kernel); K per segment -> N of the GEMM")
+        L.append('    layer   kernel   fp16x2 us   fp16x1 us   ratio')
+        for n in names:
+            L.append(f'    {n:7s} {plan[n].fwd:6s} {t1[n]:11.1f} {ta[n]:11.1f} {t1[n] / ta[n]:7.2f}')
+        L.append(f'    all pointwise launches: fp16x2 {sum(t1.values()):.1f} us, fp16x1 {sum(ta.values()):.1f} us, ratio {sum(t1.values()) / sum(ta.values()):.2f}')
+        L.append('')
+
     # ---- accuracy
     from _h1_ref import h1_unet_forward
     with torch.no_grad():
-        y2, y1 = u2(crop1).clone(), u1(crop1).clone()
-        f2, f1 = u2(frame).clone(), u1(frame).clone()
+        y2, y1, ya = u2(crop1).clone(), u1(crop1).clone(), ua(crop1).clone()
+        f2, f1, fa = u2(frame).clone(), u1(frame).clone(), ua(frame).clone()
     sd64 = {k: v.double().cuda() for k, v in sd_u.items()}
     exact = h1_unet_forward(sd64, crop1)
     rel = lambda p, q: float((p.double() - q.double()).norm() / q.double().norm())
@@ -161,6 +185,11 @@ def main():
     L.append(f'  512 x 512 crop against the float64 forward of the same weights: fp16x1 PSNR {psnr(y1, exact):.1f} dB (relative L2 {rel(y1, exact):.2e}), '
              f'fp16x2 PSNR {psnr(y2, exact):.1f} dB (relative L2 {rel(y2, exact):.2e})')
     L.append(f'  whole frame, fp16x1 against fp16x2: PSNR {psnr(f1, f2):.1f} dB, relative L2 {rel(f1, f2):.2e}, max |difference| {float((f1 - f2).abs().max()):.2e} (max |output| {float(f2.abs().max()):.2e})')
+    L.append(f'  512 x 512 crop against the float64 forward: fp16_all PSNR {psnr(ya, exact):.1f} dB (relative L2 {rel(ya, exact):.2e})')
+    L.append(f'  whole frame, fp16_all against fp16x2: PSNR {psnr(fa, f2):.1f} dB, relative L2 {rel(fa, f2):.2e}, max |difference| {float((fa - f2).abs().max()):.2e}; '
+             f'fp16_all against fp16: PSNR {psnr(fa, f1):.1f} dB')
+    ma = evaluate(ua, frame, hr)['metrics'].cpu().tolist()
+    L.append(f'  evaluate(frame, target): fp16_all PSNR {ma[0]:.4f} dB SSIM {ma[1]:.6f}')
     m2 = evaluate(u2, frame, hr)['metrics'].cpu().tolist()
     m1 = evaluate(u1, frame, hr)['metrics'].cpu().tolist()
     L.append(f'  evaluate(frame, target) with untrained weights: fp16x2 PSNR {m2[0]:.4f} dB SSIM {m2[1]:.6f}; fp16x1 PSNR {m1[0]:.4f} dB SSIM {m1[1]:.6f}; '
