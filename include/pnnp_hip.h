@@ -241,7 +241,9 @@ int pnnp_conv3x3_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, co
 /* Split-K for small grids (round 6; an eval forward on ONE 512 x 512 crop gives the deep layers 16-32 output tiles for 256 CUs): pnnp_h2_splitk returns the
  * number of K slices for a layer with `chunks` = segments x ceil(C / 16) chunks of K (1 = launch as usual); with ksplit > 1 the kernel writes raw partial
  * sums into ws ([ksplit][B][H][W][Cout] floats) and a reduce kernel adds them in a fixed order (deterministic), then bias, activation, amax_y and the sign
- * bits exactly as pnnp_conv3x3_h2_fwd_f32 would have.  Another partition of the K sum: results differ from the unsplit launch by float32 rounding only. */
+ * bits exactly as pnnp_conv3x3_h2_fwd_f32 would have.  Another partition of the K sum: results differ from the unsplit launch by float32 rounding only.
+ * With ksplit > 1 the reduce kernel reads the slabs and the bias and writes y as float4: y, bias and ws must be 16-byte aligned and amax_y 4-byte aligned, else
+ * PNNP_E_INVALID and nothing is launched (the rule of the _h1_ twin below; until the two entries shared one body this entry did not check it). */
 int pnnp_h2_splitk(int B, int H, int W, int chunks, int N);
 int pnnp_conv3x3_h2_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
                                    const void* w_h2, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y,

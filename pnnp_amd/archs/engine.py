@@ -222,21 +222,17 @@ class _EngineBase:
             kind, cip, cop = self._layer(name)
             b = lambda sfx, n, dt=u8: self._buf(name + sfx, n, dev, dt)
             co, ci = (w.shape[1], w.shape[0]) if kind == 'convt' else (w.shape[0], w.shape[1])
-            if kind != '3x3' and pf == 'h1':           # (eval plans under h1_pointwise) the one-piece forward pack of a pointwise layer; no backward-data pack exists
-                fkn = (9 * ci, co) if kind == 's2' else (ci, 4 * co) if kind == 'convt' else (ci, co)
-                f = b(':h1mf', ops.h1_pointwise_weight_bytes(*fkn))
-                self._wp[name] = (f, None, getattr(jobs, f'add_h1_{kind}')(w, f))
-                continue
-            if kind != '3x3' and pf in ('h2', 'x3'):   # 3x3 stride 2, ConvTranspose2d 2x2 stride 2, 1x1: the pointwise fp16x2 / bf16x3 GEMM kernels
-                mat = ops.h2mat_bytes if pf == 'h2' else ops.x3mat_bytes
+            if kind != '3x3' and pf in ('h2', 'x3', 'h1'):   # 3x3 stride 2, ConvTranspose2d 2x2 stride 2, 1x1: the pointwise fp16x2 / bf16x3 / fp16x1 GEMM kernels
+                # pack size, buffer suffix of the forward and of the backward-data pack ('h1': eval plans under h1_pointwise, the one-piece forward pack alone)
+                mat, sf, sd = {'h2': (ops.h2mat_bytes, ':h2mf', ':h2md'), 'x3': (ops.x3mat_bytes, ':x3f', ':x3d'), 'h1': (ops.h1_pointwise_weight_bytes, ':h1mf', None)}[pf]
                 if kind == 's2':                       # (K, N) of the forward GEMM, of the backward-data GEMM, and how many of those
                     fkn, dkn, nd = (9 * ci, co), (co, ci), 9
                 elif kind == 'convt':
                     fkn, dkn, nd = (ci, 4 * co), (4 * co, ci), 1
                 else:
                     fkn, dkn, nd = (ci, co), (co, ci), 1
-                f, d = b(':h2mf' if pf == 'h2' else ':x3f', mat(*fkn)), b(':h2md' if pf == 'h2' else ':x3d', nd * mat(*dkn)) if pd else None
-                self._wp[name] = (f, d, getattr(jobs, f'add_{pf}_{kind}')(w, f, d))
+                f, d = b(sf, mat(*fkn)), b(sd, nd * mat(*dkn)) if pd and sd else None
+                self._wp[name] = (f, d, getattr(jobs, f'add_{pf}_{kind}')(*((w, f) if sd is None else (w, f, d))))
                 continue
             if kind in ('s2', 'convt'):                # the direct kernels (their own weight layouts)
                 f, d = b(':f', w.numel(), f32), b(':d', w.numel(), f32) if pd else None
@@ -355,36 +351,40 @@ class _EngineBase:
         bits = a['bits:' + name] = T.bufs.bits(name, B, h, w, cout, T.dev)
         return bits
 
+    @staticmethod
+    def _op(name):
+        """The ops wrapper of a layer in one of the two fp16 families, by its per-family name ('conv_h1_fwd_pool'): one arm serves 'h2' and 'h1'.  Looked up
+        per call and under that name, so that whatever wraps ``ops.conv_h2_fwd`` & co. to record their operands (tests/test_gpu_range_census.py) sees the call."""
+        return getattr(ops, name)
+
+    @staticmethod
+    def _fam(fwd):
+        """a forward's family string (plan.py) as (family, variant): 'h1+splitk' -> ('h1', 'splitk'), 'x3' -> ('x3', '')"""
+        fam, _, var = fwd.partition('+')
+        return fam, var
+
     def _conv3_fwd(self, plan, name, T, a, x1, x2, bias, y, cout, act, residual=None, fill=None):
-        """``fill``: x1 has no amax yet (no producer with a fused one): an fp16x2 layer fills slot ``fill`` with a launch of its own first"""
+        """``fill``: x1 has no amax yet (no producer with a fused one): an fp16 layer fills slot ``fill`` with a launch of its own first"""
         s, (f, _, wslot) = plan[name], self._wp[name]
-        if s.fwd in ('h1', 'h1+splitk'):                     # (eval only: no sign bits) the fp16x1 twins of the two launches below
+        fam, var = self._fam(s.fwd)
+        f16 = fam in ('h2', 'h1')                            # both fp16 families: one arm, the family picks the ops wrapper (h1: eval plans only)
+        if f16:
+            bits = self._bits(plan, name, T, a, y, cout, act) if fam == 'h2' and residual is None else None      # sign bits: fp16x2 only
             if fill is not None:
                 T.put(x1, fill, fused=False)
-            ax2 = T.of(x2) if x2 is not None else None
-            if s.fwd == 'h1+splitk':
-                ops.conv_h1_fwd_splitk(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev),
-                                       amax_x2=ax2, amax_y=T.slot(name))
+            ax1, ax2 = T.of(x1), T.of(x2) if x2 is not None else None
+            if var == 'splitk':                              # a small grid: K in slices, one reduce (bias, activation, amax, sign bits)
+                self._op(f'conv_{fam}_fwd_splitk')(x1, x2, f, wslot, bias, y, cout, act, ax1, s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev),
+                                                   amax_x2=ax2, amax_y=T.slot(name), bits_y=bits)
             else:
-                ops.conv_h1_fwd(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), ax2, amax_y=T.slot(name), residual=residual)
-            return T.put(y, name, fused=True)
-        if s.fwd in ('h2', 'h2+splitk'):
-            bits = self._bits(plan, name, T, a, y, cout, act) if residual is None else None
-            if fill is not None:
-                T.put(x1, fill, fused=False)
-        if s.fwd == 'h2+splitk':                             # a small grid: K in slices, one reduce (bias, activation, amax, sign bits)
-            ops.conv_h2_fwd_splitk(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev),
-                                   amax_x2=T.of(x2) if x2 is not None else None, amax_y=T.slot(name), bits_y=bits)
-        elif s.fwd == 'h2':
-            ops.conv_h2_fwd(x1, x2, f, wslot, bias, y, cout, act, T.of(x1), T.of(x2) if x2 is not None else None, amax_y=T.slot(name),
-                            bits_y=bits, residual=residual)
+                self._op(f'conv_{fam}_fwd')(x1, x2, f, wslot, bias, y, cout, act, ax1, ax2, amax_y=T.slot(name), bits_y=bits, residual=residual)
         elif s.fwd == 'x3':
             ops.conv_x3_fwd(x1, x2, f, bias, y, cout, act, residual=residual)
         elif s.fwd == 'wino':
             ops.conv_wino_fwd(x1, x2, f, bias, y, cout, act, residual=residual)
         else:
             ops.conv_fwd(x1, x2, f, bias, y, cout, 9, act, residual=residual)
-        return T.put(y, name, fused=s.fwd.startswith('h2'))
+        return T.put(y, name, fused=f16)
 
     def _first_fwd(self, plan, name, T, a, x, w, bias, y, cout, act, fill=None):
         if plan[name].fwd != 'thin':
@@ -398,13 +398,11 @@ class _EngineBase:
     def _conv3_pool_fwd(self, plan, name, T, a, x, bias, y, pooled, codes, cout, act):
         """a 3x3 layer and the MaxPool2d(2) behind it: y, pooled and (if not None) the argmax + sign codes"""
         s, (f, _, wslot) = plan[name], self._wp[name]
-        if s.fwd == 'h2+pool':
-            # the layer writes the pooled map, the codes, its amax (the pooled map is a subset) and the sign bits from its own epilogue
-            ops.conv_h2_fwd_pool(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name),
-                                 bits_y=self._bits(plan, name, T, a, y, cout, act))
-            T.put(y, name, fused=True)
-        elif s.fwd == 'h1+pool':
-            ops.conv_h1_fwd_pool(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name))
+        fam, var = self._fam(s.fwd)
+        if var == 'pool' and fam in ('h2', 'h1'):
+            # the layer writes the pooled map, the codes, its amax (the pooled map is a subset) and (fp16x2) the sign bits from its own epilogue
+            self._op(f'conv_{fam}_fwd_pool')(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name),
+                                             bits_y=self._bits(plan, name, T, a, y, cout, act) if fam == 'h2' else None)
             T.put(y, name, fused=True)
         elif s.fwd == 'x3+pool':
             # the layer writes the pooled map and the codes from its own epilogue (csrc/conv_x3s.hip)
@@ -422,15 +420,13 @@ class _EngineBase:
             y = self._conv3_fwd(plan, name, T, a, x, None, bias, T.bufs.get(name, yshape, T.dev), yshape[3], act)
             self._head_fwd(plan, hname, T, y, hw, hb, out, res)
             return y
-        # both layers in one kernel (csrc/conv_h2s.hip EK_HEAD): the output planes come straight from the accumulators; the 3x3 layer's map
-        # is stored (with its sign bits and amax) only for a backward pass -- an eval forward neither writes nor re-reads it
+        # both layers in one kernel (csrc/conv_s.h EK_HEAD; fp16x2 or, in eval plans, fp16x1): the output planes come straight from the accumulators; the
+        # 3x3 layer's map is stored (with its sign bits and amax) only for a backward pass -- an eval forward neither writes nor re-reads it
         f, _, wslot = self._wp[name]
-        if plan[name].fwd == 'h1+head':                      # (eval only: the 32-channel map is never stored)
-            ops.conv_h1_fwd_head(x, None, f, wslot, bias, None, yshape[3], act, T.of(x), hw, hb, out, residual=res)
-            return None
+        fam = self._fam(plan[name].fwd)[0]
         y = T.bufs.get(name, yshape, T.dev) if plan.train else None
-        ops.conv_h2_fwd_head(x, None, f, wslot, bias, y, yshape[3], act, T.of(x), hw, hb, out, amax_y=T.slot(name) if plan.train else None,
-                             bits_y=self._bits(plan, name, T, a, y, yshape[3], act), residual=res)
+        self._op(f'conv_{fam}_fwd_head')(x, None, f, wslot, bias, y, yshape[3], act, T.of(x), hw, hb, out, amax_y=T.slot(name) if plan.train else None,
+                                         bits_y=self._bits(plan, name, T, a, y, yshape[3], act) if fam == 'h2' else None, residual=res)
         return T.put(y, name, fused=True) if plan.train else None
 
     def _head_fwd(self, plan, name, T, x, w, bias, out, res):
@@ -514,10 +510,8 @@ class _EngineBase:
     def _s2_fwd(self, plan, name, T, x, bias, y, cout):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
-        if fam == 'h2':
-            ops.conv_s2_h2_fwd(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
-        elif fam == 'h1':                                    # (eval only, ConvPolicy.h1_pointwise) the fp16x1 twin
-            ops.conv_s2_h1_fwd(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
+        if fam in ('h2', 'h1'):                              # ('h1': eval plans only, ConvPolicy.h1_pointwise)
+            self._op(f'conv_s2_{fam}_fwd')(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
         elif fam == 'x3':
             ops.conv_s2_x3_fwd(x, f, bias, y, cout, amax_y=T.slot(name) if plan.h2 else None)
         else:
@@ -549,10 +543,8 @@ class _EngineBase:
     def _conv1_fwd(self, plan, name, T, x1, x2, bias, y, cout, act):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
-        if fam == 'h2':
-            ops.conv1x1_h2_fwd(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
-        elif fam == 'h1':
-            ops.conv1x1_h1_fwd(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
+        if fam in ('h2', 'h1'):
+            self._op(f'conv1x1_{fam}_fwd')(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
         elif fam == 'x3':
             ops.conv1x1_x3_fwd(x1, x2, f, bias, y, cout, act)
         else:
@@ -577,10 +569,8 @@ class _EngineBase:
     def _convt_fwd(self, plan, name, T, x, bias, y, cout):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
-        if fam == 'h2':
-            ops.convt_h2_fwd(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
-        elif fam == 'h1':
-            ops.convt_h1_fwd(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
+        if fam in ('h2', 'h1'):
+            self._op(f'convt_{fam}_fwd')(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
         elif fam == 'x3':
             ops.convt_x3_fwd(x, f, bias, y, cout, amax_y=T.slot(name) if plan.h2 else None)
         else:

@@ -112,6 +112,124 @@ int s2_bwd_args(IgemmArgs& a, int cls, const float* g, int Cout, float* dx, int 
     return ns;
 }
 
+// ---- the two fp16 families (fp16x2 "h2": csrc/conv_h2s.hip, csrc/gemm_h2s.hip; fp16x1 "h1", eval forward only: csrc/conv_h1s.hip, csrc/gemm_h1s.hip).
+// Their forward layers take the same H2Args; everything the entry layer does differently for one of them is in this record.
+struct F16Family {
+    int (*conv3)(const H2Args&, int, hipStream_t);       // the 3x3 launcher
+    int (*pointwise)(const H2Args&, hipStream_t);        // the pointwise launcher
+    int pack_bytes;                                      // of one 32-column block x 32-channel item of a pointwise pack
+    bool sign_bits;                                      // a 3x3 forward may write the sign bits of its activated output
+};
+const F16Family FAM_H2{pnnp_igemm_h2s_launch, pnnp_gemm_h2s_launch, 4096, true};
+const F16Family FAM_H1{pnnp_igemm_h1s_launch, pnnp_gemm_h1s_launch, 2048, false};
+
+// the amax slots of a launch (csrc/h2.h): K segments 0 / 1 (in1 null without a second segment), the weight pack, destination 0 -- which the 3x3 kernels
+// take from H2Args and the pointwise kernels from the IgemmArgs inside it (where their bf16x3 twin reports it)
+enum SlotOf { CONV3, POINTWISE };
+void amax_slots(H2Args& a, SlotOf k, const unsigned* in0, const unsigned* in1, const unsigned* w, unsigned* out0) {
+    a.amax_in[0] = in0; a.amax_in[1] = in1; a.amax_w = w;
+    (k == CONV3 ? a.amax_out[0] : a.g.amax_out[0]) = out0;
+}
+
+int conv3_fwd(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w, const unsigned* amax_w,
+              const float* bias, const float* residual, float* y, unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w || !y || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w, bias, residual, y, B, H, W, Cout, act);
+    amax_slots(a, CONV3, amax_x1, x2 ? amax_x2 : nullptr, amax_w, amax_y);
+    if (f.sign_bits) { a.bits_out = bits_y; a.bits_nblk[0] = (Cout + 31) / 32; }
+    return f.conv3(a, C1, as_stream(stream));
+}
+
+int conv3_fwd_splitk(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w,
+                     const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act, int ksplit, float* ws,
+                     int64_t ws_floats, void* stream) {
+    if (ksplit <= 1) return conv3_fwd(f, x1, C1, amax_x1, x2, C2, amax_x2, w, amax_w, bias, nullptr, y, amax_y, bits_y, B, H, W, Cout, act, stream);
+    if (!x1 || !w || !y || !ws || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (Cout & 31)) return PNNP_E_INVALID;
+    // (the reduce kernel reads the slabs and the bias and writes y as float4; the slot takes an atomicMax.  The first launch's destination is ws and its
+    // bias null, so the launcher's own validation never sees y or bias)
+    if (((((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)ws)) & 15) || (((uintptr_t)amax_y) & 3)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    if (ws_floats < (int64_t)ksplit * B * H * W * Cout) return PNNP_E_WORKSPACE;
+    if ((int64_t)ksplit * B >= (1 << 20)) return PNNP_E_UNSUPPORTED;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w, nullptr, nullptr, ws, B, H, W, Cout, 0);
+    amax_slots(a, CONV3, amax_x1, x2 ? amax_x2 : nullptr, amax_w, nullptr);
+    a.ksplit = ksplit;
+    const int rc = f.conv3(a, C1, as_stream(stream));
+    if (rc != PNNP_OK) return rc;
+    return pnnp_h2_splitk_reduce_launch(ws, ksplit, bias, y, bits_y, amax_y, B, H, W, Cout, act, as_stream(stream));
+}
+
+int conv3_fwd_head(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w,
+                   const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y, const float* head_w, const float* head_b, const float* head_res,
+                   float* head_out, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w || !head_w || !head_out || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (Cout != 32) return PNNP_E_UNSUPPORTED;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w, bias, nullptr, y, B, H, W, Cout, act);
+    amax_slots(a, CONV3, amax_x1, x2 ? amax_x2 : nullptr, amax_w, y ? amax_y : nullptr);
+    if (f.sign_bits) { a.bits_out = y ? bits_y : nullptr; a.bits_nblk[0] = 1; }
+    a.head_w = head_w; a.head_b = head_b; a.head_res = head_res; a.head_out = head_out;
+    return f.conv3(a, C1, as_stream(stream));
+}
+
+int conv3_fwd_pool(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w,
+                   const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes, unsigned* amax_y, unsigned* bits_y, int B, int H, int W,
+                   int Cout, int act, void* stream) {
+    if (!x1 || !w || !y || !pooled || !codes || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (H & 1) || (W & 1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args a{};
+    fwd_args(a.g, x1, C1, x2, C2, w, bias, nullptr, y, B, H, W, Cout, act);
+    a.g.pool_dst = pooled; a.g.pool_codes = codes; a.g.pool_cs = Cout;
+    amax_slots(a, CONV3, amax_x1, x2 ? amax_x2 : nullptr, amax_w, amax_y);      // (the pooled map is a subset of y)
+    if (f.sign_bits) { a.bits_out = bits_y; a.bits_nblk[0] = (Cout + 31) / 32; }
+    return f.conv3(a, C1, as_stream(stream));
+}
+
+// a pointwise launch of either family: K (channels of a segment) and N (GEMM columns) in multiples of 32 (pnnp_gemm_h2_supported)
+int gemm_f16_go(const F16Family& f, H2Args& h, int chan_per_seg, hipStream_t st) {
+    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg);
+    if (rc != PNNP_OK) return rc;
+    if (!pnnp_gemm_h2_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
+    h.g.seg_channels = chan_per_seg;
+    h.g.chunks_per_seg = chan_per_seg / 32;                         // both schemes (csrc/gemm_s.h) walk K in 32-channel items
+    if ((int64_t)(h.g.Ntot / 32) * h.g.nseg * h.g.chunks_per_seg * f.pack_bytes >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+    return f.pointwise(h, st);
+}
+
+int convt_fwd(const F16Family& f, const float* x, int Cin, const unsigned* amax_x, const void* w, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
+              int B, int H, int W, int Cout, void* stream) {
+    if (!x || !w || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    convt_fwd_args(h.g, x, Cin, w, bias, y, B, H, W, Cout);
+    amax_slots(h, POINTWISE, amax_x, nullptr, amax_w, amax_y);
+    return gemm_f16_go(f, h, Cin, as_stream(stream));
+}
+
+int conv1x1_fwd(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w, const unsigned* amax_w,
+                const float* bias, const float* residual, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x1 || !w || !y || !amax_x1 || !amax_w || (x2 && !amax_x2) || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    fwd_args(h.g, x1, C1, x2, C2, w, bias, residual, y, B, H, W, Cout, act);
+    amax_slots(h, POINTWISE, amax_x1, x2 ? amax_x2 : nullptr, amax_w, amax_y);
+    return gemm_f16_go(f, h, C1, as_stream(stream));
+}
+
+int conv_s2_fwd(const F16Family& f, const float* x, int Cin, const unsigned* amax_x, const void* w, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
+                int B, int H, int W, int Cout, int act, void* stream) {
+    if (!x || !w || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
+    if (B == 0) return PNNP_OK;
+    H2Args h{};
+    s2_fwd_args(h.g, x, Cin, w, bias, y, B, H, W, Cout, act);
+    amax_slots(h, POINTWISE, amax_x, nullptr, amax_w, amax_y);
+    return gemm_f16_go(f, h, Cin, as_stream(stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,125 +357,58 @@ int pnnp_conv3x3_x3_bwd_data_res_f32(const float* g, int Cout, const void* w_x3_
 // (pnnp_h2_bits_words words) and backward-data may take its act' masks as those bits instead of the float32 activation.
 int pnnp_h2_supported(int K, int N) { return (K > 0 && (K % 8) == 0 && N > 0 && (N % 32) == 0 && N <= 1024) ? 1 : 0; }
 
-int pnnp_conv3x3_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                            const void* w_h2, const unsigned* amax_w, const float* bias, const float* residual, float* y,
-                            unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h2 || !y || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h2, bias, residual, y, B, H, W, Cout, act);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;
-    a.bits_out = bits_y; a.bits_nblk[0] = (Cout + 31) / 32;
-    return pnnp_igemm_h2s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2, const unsigned* amax_w,
+                            const float* bias, const float* residual, float* y, unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd(FAM_H2, x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, residual, y, amax_y, bits_y, B, H, W, Cout, act, stream);
 }
 
 // small grids: K cut into `ksplit` slices (pnnp_h2_splitk), raw partial sums into ws [ksplit][B][H][W][Cout], then one reduce kernel (bias, activation,
-// amax, sign bits); ksplit <= 1: the ordinary launch
-int pnnp_conv3x3_h2_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                   const void* w_h2, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y,
-                                   int B, int H, int W, int Cout, int act, int ksplit, float* ws, int64_t ws_floats, void* stream) {
-    if (ksplit <= 1) return pnnp_conv3x3_h2_fwd_f32(x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, nullptr, y, amax_y, bits_y, B, H, W, Cout, act, stream);
-    if (!x1 || !w_h2 || !y || !ws || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (Cout & 31)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    if (ws_floats < (int64_t)ksplit * B * H * W * Cout) return PNNP_E_WORKSPACE;
-    if ((int64_t)ksplit * B >= (1 << 20)) return PNNP_E_UNSUPPORTED;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h2, nullptr, nullptr, ws, B, H, W, Cout, 0);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w;
-    a.ksplit = ksplit;
-    const int rc = pnnp_igemm_h2s_launch(a, C1, as_stream(stream));
-    if (rc != PNNP_OK) return rc;
-    return pnnp_h2_splitk_reduce_launch(ws, ksplit, bias, y, bits_y, amax_y, B, H, W, Cout, act, as_stream(stream));
+// amax, sign bits); ksplit <= 1: the ordinary launch.  The reduce kernel moves float4: y, bias and ws must be 16-byte aligned and amax_y 4-byte aligned,
+// else PNNP_E_INVALID before anything is launched (the rule of the _h1_ twin; one body serves both: conv3_fwd_splitk above)
+int pnnp_conv3x3_h2_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2,
+                                   const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act,
+                                   int ksplit, float* ws, int64_t ws_floats, void* stream) {
+    return conv3_fwd_splitk(FAM_H2, x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, y, amax_y, bits_y, B, H, W, Cout, act, ksplit, ws, ws_floats, stream);
 }
 
 // conv3x3 + activation + the network's 1x1 head (archs/Unet.py:93-94: conv9_2, lrelu, conv10_1) in one kernel; y null: the 32-channel map is not stored
-int pnnp_conv3x3_h2_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                 const void* w_h2, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, unsigned* bits_y,
-                                 const float* head_w, const float* head_b, const float* head_res, float* head_out,
-                                 int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h2 || !head_w || !head_out || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (Cout != 32) return PNNP_E_UNSUPPORTED;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h2, bias, nullptr, y, B, H, W, Cout, act);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = y ? amax_y : nullptr;
-    a.bits_out = y ? bits_y : nullptr; a.bits_nblk[0] = 1;
-    a.head_w = head_w; a.head_b = head_b; a.head_res = head_res; a.head_out = head_out;
-    return pnnp_igemm_h2s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h2_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2, const unsigned* amax_w,
+                                 const float* bias, float* y, unsigned* amax_y, unsigned* bits_y, const float* head_w, const float* head_b, const float* head_res,
+                                 float* head_out, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd_head(FAM_H2, x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, y, amax_y, bits_y, head_w, head_b, head_res, head_out, B, H, W, Cout, act, stream);
 }
 
-int pnnp_conv3x3_h2_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                 const void* w_h2, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
-                                 unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h2 || !y || !pooled || !codes || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (H & 1) || (W & 1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h2, bias, nullptr, y, B, H, W, Cout, act);
-    a.g.pool_dst = pooled; a.g.pool_codes = codes; a.g.pool_cs = Cout;
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;      // (the pooled map is a subset of y)
-    a.bits_out = bits_y; a.bits_nblk[0] = (Cout + 31) / 32;
-    return pnnp_igemm_h2s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h2_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2, const unsigned* amax_w,
+                                 const float* bias, float* y, float* pooled, unsigned char* codes, unsigned* amax_y, unsigned* bits_y, int B, int H, int W, int Cout, int act,
+                                 void* stream) {
+    return conv3_fwd_pool(FAM_H2, x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, y, pooled, codes, amax_y, bits_y, B, H, W, Cout, act, stream);
 }
 
 // ---------------------------------------------------------------- the same forward layers with ONE fp16 piece per operand (fp16x1, csrc/conv_h1s.hip)
-// Eval forward only: the h2 entries' contracts without sign bits; w_h1: the kind-7 pack (pnnp_pack_jobs_add_h1).  Alignment of every pointer a kernel touches
-// with vector accesses is checked here or in the launcher (csrc/conv_s.h conv_s_validate): y, bias and the workspace of the split-K entry included.
+// Eval forward only: the h2 entries' contracts without sign bits (the same bodies, FAM_H1); w_h1: the kind-7 pack (pnnp_pack_jobs_add_h1).  Alignment of every
+// pointer a kernel touches with vector accesses is checked here or in the launcher (csrc/conv_s.h conv_s_validate): y, bias and the workspace of the split-K entry included.
 int pnnp_h1_supported(int K, int N) { return pnnp_h2_supported(K, N); }
 
-int pnnp_conv3x3_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                            const void* w_h1, const unsigned* amax_w, const float* bias, const float* residual, float* y,
-                            unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h1 || !y || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, residual, y, B, H, W, Cout, act);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;
-    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                            const float* bias, const float* residual, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, residual, y, amax_y, nullptr, B, H, W, Cout, act, stream);
 }
 
-int pnnp_conv3x3_h1_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                   const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
-                                   int B, int H, int W, int Cout, int act, int ksplit, float* ws, int64_t ws_floats, void* stream) {
-    if (ksplit <= 1) return pnnp_conv3x3_h1_fwd_f32(x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, nullptr, y, amax_y, B, H, W, Cout, act, stream);
-    if (!x1 || !w_h1 || !y || !ws || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (Cout & 31)) return PNNP_E_INVALID;
-    // (the reduce kernel reads the slabs and the bias and writes y as float4; the slot takes an atomicMax)
-    if (((((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)ws)) & 15) || (((uintptr_t)amax_y) & 3)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    if (ws_floats < (int64_t)ksplit * B * H * W * Cout) return PNNP_E_WORKSPACE;
-    if ((int64_t)ksplit * B >= (1 << 20)) return PNNP_E_UNSUPPORTED;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h1, nullptr, nullptr, ws, B, H, W, Cout, 0);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w;
-    a.ksplit = ksplit;
-    const int rc = pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
-    if (rc != PNNP_OK) return rc;
-    return pnnp_h2_splitk_reduce_launch(ws, ksplit, bias, y, nullptr, amax_y, B, H, W, Cout, act, as_stream(stream));
+int pnnp_conv3x3_h1_fwd_splitk_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1,
+                                   const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, int ksplit, float* ws,
+                                   int64_t ws_floats, void* stream) {
+    return conv3_fwd_splitk(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, y, amax_y, nullptr, B, H, W, Cout, act, ksplit, ws, ws_floats, stream);
 }
 
-int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
-                                 const float* head_w, const float* head_b, const float* head_res, float* head_out,
-                                 int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h1 || !head_w || !head_out || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (Cout != 32) return PNNP_E_UNSUPPORTED;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, nullptr, y, B, H, W, Cout, act);
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = y ? amax_y : nullptr;
-    a.head_w = head_w; a.head_b = head_b; a.head_res = head_res; a.head_out = head_out;
-    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                                 const float* bias, float* y, unsigned* amax_y, const float* head_w, const float* head_b, const float* head_res, float* head_out, int B,
+                                 int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd_head(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, y, amax_y, nullptr, head_w, head_b, head_res, head_out, B, H, W, Cout, act, stream);
 }
 
-int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2,
-                                 const void* w_h1, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
-                                 unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h1 || !y || !pooled || !codes || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1) || (H & 1) || (W & 1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args a{};
-    fwd_args(a.g, x1, C1, x2, C2, w_h1, bias, nullptr, y, B, H, W, Cout, act);
-    a.g.pool_dst = pooled; a.g.pool_codes = codes; a.g.pool_cs = Cout;
-    a.amax_in[0] = amax_x1; a.amax_in[1] = x2 ? amax_x2 : nullptr; a.amax_w = amax_w; a.amax_out[0] = amax_y;      // (the pooled map is a subset of y)
-    return pnnp_igemm_h1s_launch(a, C1, as_stream(stream));
+int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                                 const float* bias, float* y, float* pooled, unsigned char* codes, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd_pool(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, y, pooled, codes, amax_y, nullptr, B, H, W, Cout, act, stream);
 }
 
 // mask1 / mask2: the float32 activation, or bits1 / bits2: its sign bits from the forward kernel (then the float32 pointer is not read)
@@ -371,7 +422,7 @@ int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_
     bwd_args(a.g, g, Cout, w_h2_dgrad, dx1, C1, mask1, mode1, accum1, dx2, C2, mask2, mode2, accum2, B, H, W);
     if (bits1) a.g.mask_mode[0] = mode1;
     if (bits2 && dx2) a.g.mask_mode[1] = mode2;
-    a.amax_in[0] = amax_g; a.amax_w = amax_w; a.amax_out[0] = amax_dx1; a.amax_out[1] = dx2 ? amax_dx2 : nullptr;
+    amax_slots(a, CONV3, amax_g, nullptr, amax_w, amax_dx1); a.amax_out[1] = dx2 ? amax_dx2 : nullptr;
     a.bits_in[0] = bits1; a.bits_in[1] = dx2 ? bits2 : nullptr; a.bits_nblk[0] = (C1 + 31) / 32; a.bits_nblk[1] = (C2 + 31) / 32;
     return pnnp_igemm_h2s_launch(a, Cout, as_stream(stream));
 }
@@ -389,7 +440,7 @@ int pnnp_conv3x3_h2_bwd_data_unpool_f32(const float* g, int Cout, const unsigned
     H2Args a{};
     bwd_args(a.g, g, Cout, static_cast<const char*>(w_h2_dgrad) + (col0 >> 5) * blk_bytes, dx, C, nullptr, 0, accum, nullptr, 0, nullptr, 0, 0, B, H, W);
     if (bits) a.g.mask_mode[0] = mode;
-    a.amax_in[0] = amax_g; a.amax_w = amax_w; a.amax_out[0] = amax_dx;
+    amax_slots(a, CONV3, amax_g, nullptr, amax_w, amax_dx);
     a.bits_in[0] = bits; a.bits_nblk[0] = (C + 31) / 32;
     a.dgrad_plain = !bits && !accum;
     if (gp || codes) {
@@ -407,7 +458,7 @@ int pnnp_conv3x3_h2_bwd_data_res_f32(const float* g, int Cout, const unsigned* a
     if (B == 0) return PNNP_OK;
     H2Args a{};
     bwd_res_args(a.g, g, Cout, w_h2_dgrad, dx, C1, addsrc, mask, mode, B, H, W);
-    a.amax_in[0] = amax_g; a.amax_w = amax_w; a.amax_out[0] = amax_dx;
+    amax_slots(a, CONV3, amax_g, nullptr, amax_w, amax_dx);
     return pnnp_igemm_h2s_launch(a, Cout, as_stream(stream));
 }
 
@@ -502,25 +553,9 @@ int pnnp_conv3x3s2_x3_bwd_data_amax_f32(const float* g, int Cout, const void* w_
 // Contracts of the _x3_ entries above + the amax slots of the fp16x2 family; weights: the kind-6 packs of pnnp_pack_jobs_add_h2_convt / _1x1.
 // K (channels of a segment) in multiples of 32, N (GEMM columns: 4 Cout for ConvTranspose2d forward) in multiples of 64.
 int pnnp_gemm_h2_supported(int K, int N) { return (K > 0 && N > 0 && K % 32 == 0 && N % 32 == 0) ? 1 : 0; }      // (round 6: 32-column tiles for N = 32 mod 64)
-namespace {
-int gemm_h2_go(H2Args& h, int chan_per_seg, hipStream_t st) {
-    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg);
-    if (rc != PNNP_OK) return rc;
-    if (!pnnp_gemm_h2_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
-    h.g.seg_channels = chan_per_seg;
-    h.g.chunks_per_seg = chan_per_seg / 32;                         // the fp16x2 scheme (csrc/gemm_h2s.hip) walks K in 32-channel items
-    if ((int64_t)(h.g.Ntot / 32) * h.g.nseg * h.g.chunks_per_seg * 4096 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
-    return pnnp_gemm_h2s_launch(h, st);
-}
-}  // namespace
-int pnnp_convt2x2_h2_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h2, const unsigned* amax_w, const float* bias, float* y,
-                             unsigned* amax_y, int B, int H, int W, int Cout, void* stream) {
-    if (!x || !w_h2 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    convt_fwd_args(h.g, x, Cin, w_h2, bias, y, B, H, W, Cout);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
-    return gemm_h2_go(h, Cin, as_stream(stream));
+int pnnp_convt2x2_h2_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h2, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, int B,
+                             int H, int W, int Cout, void* stream) {
+    return convt_fwd(FAM_H2, x, Cin, amax_x, w_h2, amax_w, bias, y, amax_y, B, H, W, Cout, stream);
 }
 int pnnp_convt2x2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w, float* dx, int Cin,
                                   const float* mask, int mode, unsigned* amax_dx, int B, int H, int W, void* stream) {
@@ -528,8 +563,8 @@ int pnnp_convt2x2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax
     if (B == 0) return PNNP_OK;
     H2Args h{};
     convt_bwd_args(h.g, g, Cout, w_h2_dgrad, dx, Cin, mask, mode, B, H, W);
-    h.g.amax_out[0] = amax_dx; h.amax_in[0] = amax_g; h.amax_w = amax_w;
-    return gemm_h2_go(h, Cout, as_stream(stream));
+    amax_slots(h, POINTWISE, amax_g, nullptr, amax_w, amax_dx);
+    return gemm_f16_go(FAM_H2, h, Cout, as_stream(stream));
 }
 // ... with the LeakyReLU' / ReLU' mask as the sign bits the 3x3 forward kernel stored for the layer's INPUT map (bits: pnnp_h2_bits_words(B, H, W, Cin) words)
 int pnnp_convt2x2_h2_bwd_data_bits_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w, float* dx, int Cin,
@@ -539,19 +574,13 @@ int pnnp_convt2x2_h2_bwd_data_bits_f32(const float* g, int Cout, const unsigned*
     H2Args h{};
     convt_bwd_args(h.g, g, Cout, w_h2_dgrad, dx, Cin, nullptr, 0, B, H, W);
     h.g.mask_mode[0] = mode;
-    h.g.amax_out[0] = amax_dx; h.amax_in[0] = amax_g; h.amax_w = amax_w;
+    amax_slots(h, POINTWISE, amax_g, nullptr, amax_w, amax_dx);
     h.bits_in[0] = bits; h.bits_nblk[0] = Cin / 32;
-    return gemm_h2_go(h, Cout, as_stream(stream));
+    return gemm_f16_go(FAM_H2, h, Cout, as_stream(stream));
 }
-int pnnp_conv1x1_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2,
-                            const unsigned* amax_w, const float* bias, const float* residual, float* y, unsigned* amax_y,
-                            int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h2 || !y || !amax_x1 || !amax_w || (x2 && !amax_x2) || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    fwd_args(h.g, x1, C1, x2, C2, w_h2, bias, residual, y, B, H, W, Cout, act);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x1; h.amax_in[1] = x2 ? amax_x2 : nullptr; h.amax_w = amax_w;
-    return gemm_h2_go(h, C1, as_stream(stream));
+int pnnp_conv1x1_h2_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h2, const unsigned* amax_w,
+                            const float* bias, const float* residual, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv1x1_fwd(FAM_H2, x1, C1, amax_x1, x2, C2, amax_x2, w_h2, amax_w, bias, residual, y, amax_y, B, H, W, Cout, act, stream);
 }
 int pnnp_conv1x1_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, int mode1, int accum1, unsigned* amax_dx1,
@@ -560,18 +589,13 @@ int pnnp_conv1x1_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_
     if (B == 0) return PNNP_OK;
     H2Args h{};
     bwd_args(h.g, g, Cout, w_h2_dgrad, dx1, C1, mask1, mode1, accum1, dx2, C2, mask2, mode2, accum2, B, H, W);
-    h.g.amax_out[0] = amax_dx1; h.amax_in[0] = amax_g; h.amax_w = amax_w;
-    return gemm_h2_go(h, Cout, as_stream(stream));
+    amax_slots(h, POINTWISE, amax_g, nullptr, amax_w, amax_dx1);
+    return gemm_f16_go(FAM_H2, h, Cout, as_stream(stream));
 }
 
-int pnnp_conv3x3s2_h2_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h2, const unsigned* amax_w, const float* bias, float* y,
-                              unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x || !w_h2 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    s2_fwd_args(h.g, x, Cin, w_h2, bias, y, B, H, W, Cout, act);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
-    return gemm_h2_go(h, Cin, as_stream(stream));
+int pnnp_conv3x3s2_h2_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h2, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, int B,
+                              int H, int W, int Cout, int act, void* stream) {
+    return conv_s2_fwd(FAM_H2, x, Cin, amax_x, w_h2, amax_w, bias, y, amax_y, B, H, W, Cout, act, stream);
 }
 int pnnp_conv3x3s2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_s2dgrad, const unsigned* amax_w, float* dx, int Cin,
                                    const float* mask, int mode, int accum, unsigned* amax_dx, int B, int H, int W, void* stream) {
@@ -581,9 +605,9 @@ int pnnp_conv3x3s2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* ama
     for (int cls = 0; cls < 4; ++cls) {                              // one launch per input-pixel parity class (pnnp_conv3x3s2_x3_bwd_data_amax_f32)
         H2Args h{};
         const int ns = s2_bwd_args(h.g, cls, g, Cout, dx, Cin, mask, mode, accum, B, H, W);
-        h.g.amax_out[0] = amax_dx; h.amax_in[0] = amax_g; h.amax_w = amax_w;
+        amax_slots(h, POINTWISE, amax_g, nullptr, amax_w, amax_dx);
         h.g.w = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w_h2_s2dgrad) + (int64_t)slice * Cout * Cin * 4);
-        const int rc = gemm_h2_go(h, Cout, as_stream(stream));
+        const int rc = gemm_f16_go(FAM_H2, h, Cout, as_stream(stream));
         if (rc != PNNP_OK) return rc;
         slice += ns;
     }
@@ -591,46 +615,19 @@ int pnnp_conv3x3s2_h2_bwd_data_f32(const float* g, int Cout, const unsigned* ama
 }
 
 // ---------------------------------------------------------------- the same FORWARD layers with ONE fp16 piece per operand (fp16x1, csrc/gemm_h1s.hip)
-// Eval forward only: the argument lists of the _h2_ forward entries above; weights: the kind-8 packs of pnnp_pack_jobs_add_h1_convt / _1x1 / _s2.
+// Eval forward only: the argument lists and the bodies of the _h2_ forward entries above; weights: the kind-8 packs of pnnp_pack_jobs_add_h1_convt / _1x1 / _s2.
 int pnnp_h1_pointwise_supported(int K, int N) { return pnnp_gemm_h2_supported(K, N); }
-namespace {
-int gemm_h1_go(H2Args& h, int chan_per_seg, hipStream_t st) {
-    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg);
-    if (rc != PNNP_OK) return rc;
-    if (!pnnp_h1_pointwise_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
-    h.g.seg_channels = chan_per_seg;
-    h.g.chunks_per_seg = chan_per_seg / 32;                         // 32-channel items, as fp16x2
-    if ((int64_t)(h.g.Ntot / 32) * h.g.nseg * h.g.chunks_per_seg * 2048 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
-    return pnnp_gemm_h1s_launch(h, st);
+int pnnp_convt_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, int B,
+                          int H, int W, int Cout, void* stream) {
+    return convt_fwd(FAM_H1, x, Cin, amax_x, w_h1, amax_w, bias, y, amax_y, B, H, W, Cout, stream);
 }
-}  // namespace
-int pnnp_convt_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y,
-                          unsigned* amax_y, int B, int H, int W, int Cout, void* stream) {
-    if (!x || !w_h1 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    convt_fwd_args(h.g, x, Cin, w_h1, bias, y, B, H, W, Cout);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
-    return gemm_h1_go(h, Cin, as_stream(stream));
+int pnnp_conv1x1_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                            const float* bias, const float* residual, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv1x1_fwd(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, residual, y, amax_y, B, H, W, Cout, act, stream);
 }
-int pnnp_conv1x1_h1_fwd_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1,
-                            const unsigned* amax_w, const float* bias, const float* residual, float* y, unsigned* amax_y,
-                            int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w_h1 || !y || !amax_x1 || !amax_w || (x2 && !amax_x2) || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    fwd_args(h.g, x1, C1, x2, C2, w_h1, bias, residual, y, B, H, W, Cout, act);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x1; h.amax_in[1] = x2 ? amax_x2 : nullptr; h.amax_w = amax_w;
-    return gemm_h1_go(h, C1, as_stream(stream));
-}
-int pnnp_conv_s2_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y,
-                            unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x || !w_h1 || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
-    if (B == 0) return PNNP_OK;
-    H2Args h{};
-    s2_fwd_args(h.g, x, Cin, w_h1, bias, y, B, H, W, Cout, act);
-    h.g.amax_out[0] = amax_y; h.amax_in[0] = amax_x; h.amax_w = amax_w;
-    return gemm_h1_go(h, Cin, as_stream(stream));
+int pnnp_conv_s2_h1_fwd_f32(const float* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y, int B,
+                            int H, int W, int Cout, int act, void* stream) {
+    return conv_s2_fwd(FAM_H1, x, Cin, amax_x, w_h1, amax_w, bias, y, amax_y, B, H, W, Cout, act, stream);
 }
 
 // ConvTranspose2d(Cin, Cout, 2, stride=2) forward   archs/Unet.py:35-47

@@ -26,6 +26,10 @@ from ._lib import PnnpError
 from .metrics import IlluminanceCorrect, quality_assess
 
 
+# precision= -> the engine switches (ConvPolicy sub-switches, set_policy) a call forces; a switch not named stays as the call finds it
+_PRECISION = {'fp32': dict(h1_eval=False), 'fp16': dict(h1_eval=True), 'fp16_all': dict(h1_eval=True, h1_pointwise=True)}
+
+
 @contextlib.contextmanager
 def _precision(net, precision):
     """``precision=`` of the functions below: None leaves the engine's policy alone; 'fp16' runs the eval forward's stride-1 3x3 layers with ONE fp16
@@ -37,45 +41,30 @@ def _precision(net, precision):
     if precision is None:
         yield
         return
-    if precision not in ('fp32', 'fp16', 'fp16_all'):
+    if precision not in _PRECISION:
         raise PnnpError(f"precision must be None, 'fp32', 'fp16' or 'fp16_all', got {precision!r}")
+    want = _PRECISION[precision]
     eng = getattr(net, 'engine', None)
     if eng is None or not hasattr(eng, 'set_policy'):
         if precision != 'fp32':
             raise PnnpError(f"precision='{precision}' needs a network with a HIP engine")
         yield
         return
-    if precision == 'fp16_all':
-        if not eng.policy.h2:
-            raise PnnpError("precision='fp16_all' needs the fp16x2 family (set_policy(h2=True)): its amax slots are what the scale is made of")
-        prev = {k: bool(getattr(eng.policy, k)) for k in ('h1_eval', 'h1_pointwise')}
-        if all(prev.values()):
-            yield
-            return
-        had = {k: k in eng._h2_sub for k in prev}
-        eng.set_policy(h1_eval=True, h1_pointwise=True)
-        try:
-            yield
-        finally:
-            eng.set_policy(**prev)
-            for k, h in had.items():
-                if not h:
-                    eng._h2_sub.pop(k, None)
-        return
-    want, prev = precision == 'fp16', bool(eng.policy.h1_eval)
-    if want and not eng.policy.h2:
-        raise PnnpError("precision='fp16' needs the fp16x2 family (set_policy(h2=True)): its amax slots are what the scale is made of")
-    if want == prev:
+    if want['h1_eval'] and not eng.policy.h2:
+        raise PnnpError(f"precision='{precision}' needs the fp16x2 family (set_policy(h2=True)): its amax slots are what the scale is made of")
+    prev = {k: bool(getattr(eng.policy, k)) for k in want}
+    if prev == want:
         yield
         return
-    had = 'h1_eval' in eng._h2_sub
-    eng.set_policy(h1_eval=want)
+    had = [k for k in want if k in eng._h2_sub]
+    eng.set_policy(**want)
     try:
         yield
     finally:
-        eng.set_policy(h1_eval=prev)
-        if not had:
-            eng._h2_sub.pop('h1_eval', None)
+        eng.set_policy(**prev)
+        for k in want:
+            if k not in had:
+                eng._h2_sub.pop(k, None)
 
 
 def forward_tiled(net, frame, patch_size, base=64, tile_batch=None, ratio=None, clamp=False, precision=None):

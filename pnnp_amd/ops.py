@@ -1,6 +1,7 @@
 """Thin ctypes wrappers of the layer-level C ABI (include/pnnp_hip.h).  Tensors are CUDA
 fp32; activations NHWC.  No CPU path: every function raises on CPU tensors."""
 import ctypes as C
+import inspect
 
 import numpy as np
 import torch
@@ -155,68 +156,28 @@ class PackJobs:
         self.keep += [w, dst]
         return slot
 
-    def add_h2_convt(self, w, fwd, dgrad):
-        """fp16x2 packs (csrc/gemm_h2s.hip) of a ConvTranspose2d(2, 2) weight; fwd / dgrad: uint8 buffers of h2mat_bytes (zero-filled), or None.
-        Returns the weight tensor's amax slot."""
-        ci, co = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h2_convt(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), ci, co, ptr(slot)), 'pack_jobs_add_h2_convt')
-        self.keep += [w, fwd, dgrad]
+    def _add_pointwise(self, fam, kind, w, fwd, dgrad=None):
+        """The pack jobs of a pointwise layer's weight: ``fam`` 'x3' (csrc/gemm_x3.hip) | 'h2' (csrc/gemm_h2s.hip) | 'h1' (csrc/gemm_h1s.hip), ``kind`` 'convt'
+        (ConvTranspose2d(2, 2), [Cin][Cout][2][2]) | '1x1' | 's2' (stride-2 3x3).  fwd / dgrad: zero-filled uint8 buffers of x3mat_bytes / h2mat_bytes /
+        h1_pointwise_weight_bytes of the GEMM's (K, N), or None; h1 is forward only and has no dgrad.  The fp16 families scale by the weight tensor's amax
+        slot, which is returned (x3: None)."""
+        name = f'pack_jobs_add_{fam}_{kind}'
+        bufs = [fwd] if fam == 'h1' else [fwd, dgrad]
+        slot = None if fam == 'x3' else self.weight_slot(w)
+        check(getattr(_prep(), 'pnnp_' + name)(self.jobs, C.byref(self.n), self.cap, ptr(w), *[ptr(b) for b in bufs], w.shape[0], w.shape[1],
+                                               *([] if slot is None else [ptr(slot)])), name)
+        self.keep += [w] + bufs
         return slot
 
-    def add_h2_1x1(self, w, fwd, dgrad):
-        co, ci = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h2_1x1(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci, ptr(slot)), 'pack_jobs_add_h2_1x1')
-        self.keep += [w, fwd, dgrad]
-        return slot
-
-    def add_h2_s2(self, w, fwd, dgrad):
-        co, ci = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h2_s2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci, ptr(slot)), 'pack_jobs_add_h2_s2')
-        self.keep += [w, fwd, dgrad]
-        return slot
-
-    def add_h1_convt(self, w, fwd):
-        """The fp16x1 forward pack (csrc/gemm_h1s.hip) of a ConvTranspose2d(2, 2) weight; fwd: a zero-filled uint8 buffer of
-        h1_pointwise_weight_bytes(Cin, 4 Cout).  Returns the weight tensor's amax slot."""
-        ci, co = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h1_convt(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ci, co, ptr(slot)), 'pack_jobs_add_h1_convt')
-        self.keep += [w, fwd]
-        return slot
-
-    def add_h1_1x1(self, w, fwd):
-        """... of a 1x1 Conv2d weight; fwd: h1_pointwise_weight_bytes(Cin, Cout) bytes."""
-        co, ci = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h1_1x1(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), co, ci, ptr(slot)), 'pack_jobs_add_h1_1x1')
-        self.keep += [w, fwd]
-        return slot
-
-    def add_h1_s2(self, w, fwd):
-        """... of a stride-2 3x3 Conv2d weight; fwd: h1_pointwise_weight_bytes(9 Cin, Cout) bytes."""
-        co, ci = w.shape[0], w.shape[1]
-        slot = self.weight_slot(w)
-        check(_prep().pnnp_pack_jobs_add_h1_s2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), co, ci, ptr(slot)), 'pack_jobs_add_h1_s2')
-        self.keep += [w, fwd]
-        return slot
-
-    def add_x3_convt(self, w, fwd, dgrad):
-        ci, co = w.shape[0], w.shape[1]
-        check(_prep().pnnp_pack_jobs_add_x3_convt(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), ci, co), 'pack_jobs_add_x3_convt')
-        self.keep += [w, fwd, dgrad]
-
-    def add_x3_1x1(self, w, fwd, dgrad):
-        co, ci = w.shape[0], w.shape[1]
-        check(_prep().pnnp_pack_jobs_add_x3_1x1(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci), 'pack_jobs_add_x3_1x1')
-        self.keep += [w, fwd, dgrad]
-
-    def add_x3_s2(self, w, fwd, dgrad):
-        co, ci = w.shape[0], w.shape[1]
-        check(_prep().pnnp_pack_jobs_add_x3_s2(self.jobs, C.byref(self.n), self.cap, ptr(w), ptr(fwd), ptr(dgrad), co, ci), 'pack_jobs_add_x3_s2')
-        self.keep += [w, fwd, dgrad]
+    def add_h2_convt(self, w, fwd, dgrad): return self._add_pointwise('h2', 'convt', w, fwd, dgrad)
+    def add_h2_1x1(self, w, fwd, dgrad): return self._add_pointwise('h2', '1x1', w, fwd, dgrad)
+    def add_h2_s2(self, w, fwd, dgrad): return self._add_pointwise('h2', 's2', w, fwd, dgrad)
+    def add_h1_convt(self, w, fwd): return self._add_pointwise('h1', 'convt', w, fwd)
+    def add_h1_1x1(self, w, fwd): return self._add_pointwise('h1', '1x1', w, fwd)
+    def add_h1_s2(self, w, fwd): return self._add_pointwise('h1', 's2', w, fwd)
+    def add_x3_convt(self, w, fwd, dgrad): return self._add_pointwise('x3', 'convt', w, fwd, dgrad)
+    def add_x3_1x1(self, w, fwd, dgrad): return self._add_pointwise('x3', '1x1', w, fwd, dgrad)
+    def add_x3_s2(self, w, fwd, dgrad): return self._add_pointwise('x3', 's2', w, fwd, dgrad)
 
     def add_s2_dgrad(self, w, dst):
         co, ci = w.shape[0], w.shape[1]
@@ -471,6 +432,11 @@ def h2_bits_words(B, H, W, C_):
     return int(_prep().pnnp_h2_bits_words(int(B), int(H), int(W), int(C_)))
 
 
+def h2_splitk(B, H, W, chunks, N):
+    """K slices for a small grid (pnnp_h2_splitk): 1 = launch as usual."""
+    return int(_prep().pnnp_h2_splitk(int(B), int(H), int(W), int(chunks), int(N)))
+
+
 def amax(x, slot):
     """slot = max(slot, max |x|) as a kernel of its own (tensors whose producer has no fused amax)."""
     require_cuda(x, slot)
@@ -484,56 +450,6 @@ def h2_tile_columns(B, H, W, N, pool=False):
     return int(_prep().pnnp_h2_tile_columns(int(B), int(H), int(W), int(N), int(bool(pool))))
 
 
-def conv_h2_fwd(x1, x2, w_h2, amax_w, bias, y, cout, act, amax_x1, amax_x2=None, amax_y=None, bits_y=None, residual=None):
-    """3x3 / stride 1 / pad 1 forward on the fp16 matrix cores, fp32 operands split in two scaled pieces (contract of conv_fwd, taps=9)."""
-    require_cuda(x1, x2, w_h2, y, amax_w, amax_x1)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h2', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
-        check(_prep().pnnp_conv3x3_h2_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(residual),
-                                              ptr(y), ptr(amax_y), ptr(bits_y), B, H, W, cout, act, stream()), 'conv_h2_fwd')
-    return y
-
-
-def h2_splitk(B, H, W, chunks, N):
-    """K slices for a small grid (pnnp_h2_splitk): 1 = launch as usual."""
-    return int(_prep().pnnp_h2_splitk(int(B), int(H), int(W), int(chunks), int(N)))
-
-
-def conv_h2_fwd_splitk(x1, x2, w_h2, amax_w, bias, y, cout, act, amax_x1, ksplit, ws, amax_x2=None, amax_y=None, bits_y=None):
-    """conv_h2_fwd with K cut into ``ksplit`` slices (small grids): partial sums into ``ws`` (>= ksplit * y.numel() floats), one fixed-order reduce."""
-    require_cuda(x1, x2, w_h2, y, amax_w, amax_x1, ws)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h2', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub='splitk'):
-        check(_prep().pnnp_conv3x3_h2_fwd_splitk_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
-                                                     ptr(bits_y), B, H, W, cout, act, int(ksplit), ptr(ws), _i64(ws.numel()), stream()), 'conv_h2_fwd_splitk')
-    return y
-
-
-def conv_h2_fwd_head(x1, x2, w_h2, amax_w, bias, y, cout, act, amax_x1, head_w, head_b, out, amax_x2=None, amax_y=None, bits_y=None, residual=None):
-    """The last 3x3 layer + activation + the 1x1 head in one kernel (archs/Unet.py:93-94): ``out`` NCHW [B,4,H,W] (+ ``residual``, NCHW);
-    ``y`` None: the 32-channel map is not stored (eval forward)."""
-    require_cuda(x1, x2, w_h2, y, amax_w, amax_x1, head_w, out, residual)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h2', 2.0 * B * H * W * cout * (C1 + C2) * 9 + 2.0 * B * H * W * cout * 4, 4.0 * B * H * W * (C1 + C2 + (cout if y is not None else 0) + 4), sub='bn32'):
-        check(_prep().pnnp_conv3x3_h2_fwd_head_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
-                                                   ptr(bits_y), ptr(head_w), ptr(head_b), ptr(residual), ptr(out), B, H, W, cout, act, stream()), 'conv_h2_fwd_head')
-    return out
-
-
-def conv_h2_fwd_pool(x1, x2, w_h2, amax_w, bias, y, pooled, codes, cout, act, amax_x1, amax_x2=None, amax_y=None, bits_y=None):
-    require_cuda(x1, x2, w_h2, y, pooled, codes, amax_w, amax_x1)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h2', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + 1.25 * cout) + B * H * W * cout / 4,
-                sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):      # (+ the pooled map and its one-byte codes)
-        check(_prep().pnnp_conv3x3_h2_fwd_pool_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y),
-                                                   ptr(pooled), ptr(codes), ptr(amax_y), ptr(bits_y), B, H, W, cout, act, stream()), 'conv_h2_fwd_pool')
-    return y
-
-
 # ---- the fp16x1 ("h1") family: csrc/conv_h1s.hip -- the h2 forward entries with one fp16 piece per operand, eval forward only (no sign bits)
 def h1_supported(K, N):
     return bool(_prep().pnnp_h1_supported(int(K), int(N)))
@@ -543,47 +459,81 @@ def h1_weight_bytes(K, N):
     return int(_prep().pnnp_h1_weight_bytes(int(K), int(N)))
 
 
-def conv_h1_fwd(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, amax_x2=None, amax_y=None, residual=None):
-    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1)
+# ---- the 3x3 forward layers of both fp16 families, one wrapper per layer shape: ``fam`` = 'h2' | 'h1' picks the C entry and the _Timed kind
+# ('conv9_fwd_h2' / 'conv9_fwd_h1'); the h2 entries alone take ``bits_y``.  The per-family names below them (conv_h2_fwd, conv_h1_fwd, ...) are what
+# callers use, the engine included: what wraps or inspects ``ops.conv_h2_fwd`` (tests/test_gpu_range_census.py) sees every call and named parameters.
+def _for_family(fn, fam):
+    """``fn`` with its first parameter bound to ``fam``, as a plain function that reports the rest of ``fn``'s signature"""
+    def bound(*a, **kw):
+        return fn(fam, *a, **kw)
+    sig = inspect.signature(fn)
+    bound.__signature__ = sig.replace(parameters=list(sig.parameters.values())[1:])
+    bound.__name__, bound.__doc__ = fn.__name__.replace('f16', fam), fn.__doc__
+    return bound
+
+
+def _f16_entry(fam, name, bits_y=None):
+    """(the C entry ``name`` with FAM replaced, the arguments that stand for ``bits_y`` in its list); refuses sign bits for h1 before any call"""
+    if fam not in ('h2', 'h1') or (fam == 'h1' and bits_y is not None):
+        raise _lib.PnnpError(f'{name}: family {fam!r}' + (' writes no sign bits (bits_y)' if fam == 'h1' else ' is not an fp16 family'))
+    return getattr(_prep(), name.replace('FAM', fam)), ((ptr(bits_y),) if fam == 'h2' else ())
+
+
+def conv_f16_fwd(fam, x1, x2, w, amax_w, bias, y, cout, act, amax_x1, amax_x2=None, amax_y=None, *, bits_y=None, residual=None):
+    """3x3 / stride 1 / pad 1 forward on the fp16 matrix cores (contract of conv_fwd, taps=9): fp32 operands split on the fly in two scaled fp16 pieces
+    (h2) or rounded to one (h1)."""
+    fn, bits = _f16_entry(fam, 'pnnp_conv3x3_FAM_fwd_f32', bits_y)
+    require_cuda(x1, x2, w, y, amax_w, amax_x1)
     B, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
-        check(_prep().pnnp_conv3x3_h1_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(residual),
-                                              ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_h1_fwd')
+    with _Timed('conv9_fwd_' + fam, 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
+        check(fn(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(residual), ptr(y), ptr(amax_y), *bits,
+                 B, H, W, cout, act, stream()), f'conv_{fam}_fwd')
     return y
 
 
-def conv_h1_fwd_splitk(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, ksplit, ws, amax_x2=None, amax_y=None):
-    """conv_h1_fwd with K cut into ``ksplit`` slices (h2_splitk): partial sums into ``ws`` (>= ksplit * y.numel() floats), one fixed-order reduce."""
-    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1, ws)
+def conv_f16_fwd_splitk(fam, x1, x2, w, amax_w, bias, y, cout, act, amax_x1, ksplit, ws, amax_x2=None, amax_y=None, *, bits_y=None):
+    """conv_f16_fwd with K cut into ``ksplit`` slices (small grids, h2_splitk): partial sums into ``ws`` (>= ksplit * y.numel() floats), one fixed-order reduce."""
+    fn, bits = _f16_entry(fam, 'pnnp_conv3x3_FAM_fwd_splitk_f32', bits_y)
+    require_cuda(x1, x2, w, y, amax_w, amax_x1, ws)
     B, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub='splitk'):
-        check(_prep().pnnp_conv3x3_h1_fwd_splitk_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
-                                                     B, H, W, cout, act, int(ksplit), ptr(ws), _i64(ws.numel()), stream()), 'conv_h1_fwd_splitk')
+    with _Timed('conv9_fwd_' + fam, 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + cout), sub='splitk'):
+        check(fn(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), *bits,
+                 B, H, W, cout, act, int(ksplit), ptr(ws), _i64(ws.numel()), stream()), f'conv_{fam}_fwd_splitk')
     return y
 
 
-def conv_h1_fwd_head(x1, x2, w_h1, amax_w, bias, y, cout, act, amax_x1, head_w, head_b, out, amax_x2=None, amax_y=None, residual=None):
-    """conv_h1_fwd + the network's 1x1 head in one kernel: ``out`` NCHW [B,4,H,W] (+ ``residual``, NCHW); ``y`` None: the 32-channel map is not stored."""
-    require_cuda(x1, x2, w_h1, y, amax_w, amax_x1, head_w, out, residual)
+def conv_f16_fwd_head(fam, x1, x2, w, amax_w, bias, y, cout, act, amax_x1, head_w, head_b, out, amax_x2=None, amax_y=None, *, bits_y=None, residual=None):
+    """The last 3x3 layer + activation + the 1x1 head in one kernel (archs/Unet.py:93-94): ``out`` NCHW [B,4,H,W] (+ ``residual``, NCHW);
+    ``y`` None: the 32-channel map is not stored (eval forward)."""
+    fn, bits = _f16_entry(fam, 'pnnp_conv3x3_FAM_fwd_head_f32', bits_y)
+    require_cuda(x1, x2, w, y, amax_w, amax_x1, head_w, out, residual)
     B, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9 + 2.0 * B * H * W * cout * 4, 4.0 * B * H * W * (C1 + C2 + (cout if y is not None else 0) + 4), sub='bn32'):
-        check(_prep().pnnp_conv3x3_h1_fwd_head_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y),
-                                                   ptr(head_w), ptr(head_b), ptr(residual), ptr(out), B, H, W, cout, act, stream()), 'conv_h1_fwd_head')
+    with _Timed('conv9_fwd_' + fam, 2.0 * B * H * W * cout * (C1 + C2) * 9 + 2.0 * B * H * W * cout * 4, 4.0 * B * H * W * (C1 + C2 + (cout if y is not None else 0) + 4), sub='bn32'):
+        check(fn(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), *bits,
+                 ptr(head_w), ptr(head_b), ptr(residual), ptr(out), B, H, W, cout, act, stream()), f'conv_{fam}_fwd_head')
     return out
 
 
-def conv_h1_fwd_pool(x1, x2, w_h1, amax_w, bias, y, pooled, codes, cout, act, amax_x1, amax_x2=None, amax_y=None):
-    require_cuda(x1, x2, w_h1, y, pooled, codes, amax_w, amax_x1)
+def conv_f16_fwd_pool(fam, x1, x2, w, amax_w, bias, y, pooled, codes, cout, act, amax_x1, amax_x2=None, amax_y=None, *, bits_y=None):
+    """conv_f16_fwd + MaxPool2d(2) of its output from the same kernel: ``pooled`` and the argmax / sign ``codes`` of maxpool_fwd"""
+    fn, bits = _f16_entry(fam, 'pnnp_conv3x3_FAM_fwd_pool_f32', bits_y)
+    require_cuda(x1, x2, w, y, pooled, codes, amax_w, amax_x1)
     B, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv9_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + 1.25 * cout) + B * H * W * cout / 4,
-                sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):
-        check(_prep().pnnp_conv3x3_h1_fwd_pool_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y),
-                                                   ptr(pooled), ptr(codes), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_h1_fwd_pool')
+    with _Timed('conv9_fwd_' + fam, 2.0 * B * H * W * cout * (C1 + C2) * 9, 4.0 * B * H * W * (C1 + C2 + 1.25 * cout) + B * H * W * cout / 4,
+                sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):      # (+ the pooled map and its one-byte codes)
+        check(fn(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(pooled), ptr(codes), ptr(amax_y), *bits,
+                 B, H, W, cout, act, stream()), f'conv_{fam}_fwd_pool')
     return y
+
+
+conv_h2_fwd, conv_h1_fwd = _for_family(conv_f16_fwd, 'h2'), _for_family(conv_f16_fwd, 'h1')
+conv_h2_fwd_splitk, conv_h1_fwd_splitk = _for_family(conv_f16_fwd_splitk, 'h2'), _for_family(conv_f16_fwd_splitk, 'h1')
+conv_h2_fwd_head, conv_h1_fwd_head = _for_family(conv_f16_fwd_head, 'h2'), _for_family(conv_f16_fwd_head, 'h1')
+conv_h2_fwd_pool, conv_h1_fwd_pool = _for_family(conv_f16_fwd_pool, 'h2'), _for_family(conv_f16_fwd_pool, 'h1')
 
 
 def conv_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx1, mask1=None, bits1=None, mode1=0, accum1=0, amax_dx1=None,
@@ -653,13 +603,40 @@ def h2mat_bytes(K, N):
     return int(_prep().pnnp_h2mat_bytes(int(K), int(N)))
 
 
-def convt_h2_fwd(x, amax_x, w_h2, amax_w, bias, y, cout, amax_y=None):
-    """ConvTranspose2d(2, 2) forward on the fp16 matrix cores (csrc/gemm_h2s.hip): contract of convt_x3_fwd + the amax slots."""
-    require_cuda(x, w_h2, y, amax_x, amax_w)
+# ---- the pointwise forward layers of both fp16 families (csrc/gemm_h2s.hip, csrc/gemm_h1s.hip), as the 3x3 ones above: contracts of the _x3_ wrappers + the amax slots
+def convt_f16_fwd(fam, x, amax_x, w, amax_w, bias, y, cout, amax_y=None):
+    """ConvTranspose2d(2, 2) forward on the fp16 matrix cores: contract of convt_x3_fwd + the amax slots."""
+    fn, _ = _f16_entry(fam, 'pnnp_convt2x2_h2_fwd_f32' if fam == 'h2' else 'pnnp_convt_h1_fwd_f32')
+    require_cuda(x, w, y, amax_x, amax_w)
     B, H, W, Cin = x.shape
-    with _Timed('convt_fwd_h2', 8.0 * B * H * W * Cin * cout, 4.0 * B * H * W * (Cin + 4 * cout)):
-        check(_prep().pnnp_convt2x2_h2_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, stream()), 'convt_h2_fwd')
+    with _Timed('convt_fwd_' + fam, 8.0 * B * H * W * Cin * cout, 4.0 * B * H * W * (Cin + 4 * cout)):
+        check(fn(ptr(x), Cin, ptr(amax_x), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, stream()), f'convt_{fam}_fwd')
     return y
+
+
+def conv1x1_f16_fwd(fam, x1, amax_x1, x2, amax_x2, w, amax_w, bias, y, cout, act, *, residual=None, amax_y=None):
+    fn, _ = _f16_entry(fam, 'pnnp_conv1x1_FAM_fwd_f32')
+    require_cuda(x1, x2, w, y, amax_x1, amax_w)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv1_fwd_' + fam, 2.0 * B * H * W * cout * (C1 + C2), 4.0 * B * H * W * (C1 + C2 + cout)):
+        check(fn(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(residual), ptr(y), ptr(amax_y),
+                 B, H, W, cout, act, stream()), f'conv1x1_{fam}_fwd')
+    return y
+
+
+def conv_s2_f16_fwd(fam, x, amax_x, w, amax_w, bias, y, cout, act, amax_y=None):
+    fn, _ = _f16_entry(fam, 'pnnp_conv3x3s2_h2_fwd_f32' if fam == 'h2' else 'pnnp_conv_s2_h1_fwd_f32')
+    require_cuda(x, w, y, amax_x, amax_w)
+    B, H, W, Cin = x.shape
+    with _Timed('conv9s2_fwd_' + fam, 2.0 * B * (H // 2) * (W // 2) * cout * Cin * 9):
+        check(fn(ptr(x), Cin, ptr(amax_x), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), f'conv_s2_{fam}_fwd')
+    return y
+
+
+convt_h2_fwd, convt_h1_fwd = _for_family(convt_f16_fwd, 'h2'), _for_family(convt_f16_fwd, 'h1')
+conv1x1_h2_fwd, conv1x1_h1_fwd = _for_family(conv1x1_f16_fwd, 'h2'), _for_family(conv1x1_f16_fwd, 'h1')
+conv_s2_h2_fwd, conv_s2_h1_fwd = _for_family(conv_s2_f16_fwd, 'h2'), _for_family(conv_s2_f16_fwd, 'h1')
 
 
 def convt_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx, mask=None, mode=0, amax_dx=None, bits=None):
@@ -675,16 +652,6 @@ def convt_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx, mask=None, mode=0, amax
                                                     B, H, W, stream()), 'convt_h2_bwd_data')
 
 
-def conv1x1_h2_fwd(x1, amax_x1, x2, amax_x2, w_h2, amax_w, bias, y, cout, act, residual=None, amax_y=None):
-    require_cuda(x1, x2, w_h2, y, amax_x1, amax_w)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv1_fwd_h2', 2.0 * B * H * W * cout * (C1 + C2), 4.0 * B * H * W * (C1 + C2 + cout)):
-        check(_prep().pnnp_conv1x1_h2_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(residual), ptr(y), ptr(amax_y),
-                                              B, H, W, cout, act, stream()), 'conv1x1_h2_fwd')
-    return y
-
-
 def conv1x1_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx1, mask1=None, mode1=0, accum1=0, amax_dx1=None, dx2=None, mask2=None, mode2=0, accum2=0):
     require_cuda(g, w_h2_dgrad, dx1, dx2, amax_g, amax_w)
     B, H, W, Cout = g.shape
@@ -692,14 +659,6 @@ def conv1x1_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx1, mask1=None, mode1=0,
     with _Timed('conv1_dgrad_h2', 2.0 * B * H * W * Cout * (C1 + C2), 4.0 * B * H * W * (C1 + C2 + Cout)):
         check(_prep().pnnp_conv1x1_h2_bwd_data_f32(ptr(g), Cout, ptr(amax_g), ptr(w_h2_dgrad), ptr(amax_w), ptr(dx1), C1, ptr(mask1), mode1, int(accum1), ptr(amax_dx1),
                                                    ptr(dx2), C2, ptr(mask2), mode2, int(accum2), B, H, W, stream()), 'conv1x1_h2_bwd_data')
-
-
-def conv_s2_h2_fwd(x, amax_x, w_h2, amax_w, bias, y, cout, act, amax_y=None):
-    require_cuda(x, w_h2, y, amax_x, amax_w)
-    B, H, W, Cin = x.shape
-    with _Timed('conv9s2_fwd_h2', 2.0 * B * (H // 2) * (W // 2) * cout * Cin * 9):
-        check(_prep().pnnp_conv3x3s2_h2_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h2), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_s2_h2_fwd')
-    return y
 
 
 def conv_s2_h2_bwd_data(g, amax_g, w_h2_s2dgrad, amax_w, dx, mask=None, mode=0, accum=0, amax_dx=None):
@@ -710,7 +669,7 @@ def conv_s2_h2_bwd_data(g, amax_g, w_h2_s2dgrad, amax_w, dx, mask=None, mode=0, 
                                                      B, H, W, stream()), 'conv_s2_h2_bwd_data')
 
 
-# ---- the fp16x1 ("h1") pointwise forwards: csrc/gemm_h1s.hip -- the three h2 forward entries above with one fp16 piece per operand, eval forward only
+# ---- the fp16x1 ("h1") pointwise packs: csrc/gemm_h1s.hip, one fp16 piece per operand, eval forward only
 def h1_pointwise_supported(K, N):
     return bool(_prep().pnnp_h1_pointwise_supported(int(K), int(N)))
 
@@ -718,32 +677,6 @@ def h1_pointwise_supported(K, N):
 def h1_pointwise_weight_bytes(K, N):
     """Bytes of a kind-8 pack; K, N of the forward GEMM (ConvTranspose2d: Cin, 4 Cout; 1x1: Cin, Cout; stride 2: 9 Cin, Cout)."""
     return int(_prep().pnnp_h1_pointwise_weight_bytes(int(K), int(N)))
-
-
-def convt_h1_fwd(x, amax_x, w_h1, amax_w, bias, y, cout, amax_y=None):
-    require_cuda(x, w_h1, y, amax_x, amax_w)
-    B, H, W, Cin = x.shape
-    with _Timed('convt_fwd_h1', 8.0 * B * H * W * Cin * cout, 4.0 * B * H * W * (Cin + 4 * cout)):
-        check(_prep().pnnp_convt_h1_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, stream()), 'convt_h1_fwd')
-    return y
-
-
-def conv1x1_h1_fwd(x1, amax_x1, x2, amax_x2, w_h1, amax_w, bias, y, cout, act, residual=None, amax_y=None):
-    require_cuda(x1, x2, w_h1, y, amax_x1, amax_w)
-    B, H, W, C1 = x1.shape
-    C2 = x2.shape[3] if x2 is not None else 0
-    with _Timed('conv1_fwd_h1', 2.0 * B * H * W * cout * (C1 + C2), 4.0 * B * H * W * (C1 + C2 + cout)):
-        check(_prep().pnnp_conv1x1_h1_fwd_f32(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(residual), ptr(y), ptr(amax_y),
-                                              B, H, W, cout, act, stream()), 'conv1x1_h1_fwd')
-    return y
-
-
-def conv_s2_h1_fwd(x, amax_x, w_h1, amax_w, bias, y, cout, act, amax_y=None):
-    require_cuda(x, w_h1, y, amax_x, amax_w)
-    B, H, W, Cin = x.shape
-    with _Timed('conv9s2_fwd_h1', 2.0 * B * (H // 2) * (W // 2) * cout * Cin * 9):
-        check(_prep().pnnp_conv_s2_h1_fwd_f32(ptr(x), Cin, ptr(amax_x), ptr(w_h1), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), B, H, W, cout, act, stream()), 'conv_s2_h1_fwd')
-    return y
 
 
 def conv1x1_x3_fwd(x1, x2, w_x3, bias, y, cout, act, residual=None):

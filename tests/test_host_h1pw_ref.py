@@ -241,3 +241,67 @@ def test_precision_argument_names():
     with _precision(net, 'fp32'):
         assert not net.engine.policy.h1_eval
     assert net.engine.policy.h1_eval
+
+
+@pytest.mark.parametrize('precision', ['fp16', 'fp32', 'fp16_all'])
+def test_precision_restores_what_it_found(precision):
+    """One path over a table of forced switches (evaluate._PRECISION): whatever the engine had comes back, overrides that were not there are
+    removed again, also when the body raises; a switch the precision does not name is not touched; nothing at all is touched when the
+    switches already have the wanted values."""
+    from pnnp_amd.evaluate import _PRECISION, _precision
+    assert _PRECISION == {'fp32': dict(h1_eval=False), 'fp16': dict(h1_eval=True), 'fp16_all': dict(h1_eval=True, h1_pointwise=True)}
+    want = _PRECISION[precision]
+    for start in (dict(), dict(h1_eval=True), dict(h1_pointwise=True), dict(h1_eval=True, h1_pointwise=True), dict(h1_eval=False)):
+        class Net:
+            engine = _engine(**start)
+        net = Net()
+        pol = net.engine.policy
+        before = (pol.h1_eval, pol.h1_pointwise, dict(net.engine._h2_sub))
+        inside = {'h1_eval': pol.h1_eval, 'h1_pointwise': pol.h1_pointwise, **want}
+        for body_raises in (False, True):
+            try:
+                with _precision(net, precision):
+                    p = net.engine.policy
+                    assert (p.h1_eval, p.h1_pointwise) == (inside['h1_eval'], inside['h1_pointwise']), (start, precision)
+                    assert (p is pol) == (inside == dict(h1_eval=before[0], h1_pointwise=before[1])), (start, precision)     # untouched when already as wanted
+                    if body_raises:
+                        1 / 0
+            except ZeroDivisionError:
+                assert body_raises
+            p = net.engine.policy
+            assert (p.h1_eval, p.h1_pointwise, net.engine._h2_sub) == before, (start, precision, body_raises)
+
+
+def test_precision_fp16_under_pointwise_engine_and_messages():
+    from pnnp_amd._lib import PnnpError
+    from pnnp_amd.evaluate import _precision
+
+    class Net:
+        engine = _engine(h1_pointwise=True)                              # serves nothing yet: the pointwise switch alone changes no plan
+    net = Net()
+    with _precision(net, 'fp16'):                                        # 'fp16' leaves h1_pointwise as it finds it: here that is fp16_all's plan
+        p = net.engine.policy
+        assert p.h1_eval and p.h1_pointwise
+        assert p.plan_key() == _engine(h1_eval=True, h1_pointwise=True).policy.plan_key()
+    assert not net.engine.policy.h1_eval and net.engine.policy.h1_pointwise and net.engine._h2_sub == {'h1_pointwise': True}
+    with pytest.raises(ZeroDivisionError):
+        with _precision(net, 'fp16'):
+            1 / 0
+    assert not net.engine.policy.h1_eval and net.engine.policy.h1_pointwise and net.engine._h2_sub == {'h1_pointwise': True}
+    net.engine.set_policy(h2=False)
+    for precision in ('fp16', 'fp16_all'):                               # the messages name the precision asked for
+        with pytest.raises(PnnpError, match=f"precision='{precision}' needs the fp16x2 family"):
+            with _precision(net, precision):
+                pass
+    with _precision(net, 'fp32'):                                        # nothing to force: h1_eval is off without h2
+        pass
+
+    class NoEngine:
+        pass
+    for precision in ('fp16', 'fp16_all'):
+        with pytest.raises(PnnpError, match=f"precision='{precision}' needs a network with a HIP engine"):
+            with _precision(NoEngine(), precision):
+                pass
+    with pytest.raises(PnnpError, match="got 'bf16'"):
+        with _precision(NoEngine(), 'bf16'):
+            pass
