@@ -284,6 +284,34 @@ int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x
 int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2 /*or null*/, int C2, const unsigned* amax_x2,
                                  const void* w_h1, const unsigned* amax_w, const float* bias, float* y, float* pooled, unsigned char* codes,
                                  unsigned* amax_y /*or null*/, int B, int H, int W, int Cout, int act, void* stream);
+/* ---- ... with fp16 ACTIVATIONS ("h1a", csrc/conv_h1s.hip H1a): each entry is its _f32 twin above with an element type per side.
+ *   src_f16 != 0: x1 / x2 are fp16 NHWC tensors (both: a float32 segment beside an fp16 one cannot be asked for).  Their halves are the matrix operands as they
+ *     are -- unscaled (se_x = 0), subnormals kept; the amax slots of x1 / x2 are not read and may be null.  Fed x16 where the _f32 twin is fed float(x16) the
+ *     outputs agree bit for bit whenever max |x16| < 2^15 (the twin's scaled rounding is then exact).  C1 in multiples of 8; 16-byte aligned.
+ *   dst_f16 != 0: y (and the pooled map) are fp16: float16(v) of the float32 value v the _f32 twin stores -- ONE round to nearest even, unscaled, subnormals kept,
+ *     NOT saturated (|v| > 65504 becomes inf; NaN stays NaN).  amax_y still records max |v| BEFORE the rounding.  Codes are the twin's.
+ *   One image of a map must stay below 2 GB in ITS element size (pnnp_image_fits_es).  No residual; the split-K slabs (ws) stay float32; the head entry stores
+ *   nothing but head_out (float32 NCHW); the pool entry takes fp16 on both sides.  Everything else: PNNP_E_UNSUPPORTED /
+ *   PNNP_E_INVALID as for the twins, nothing launched, outputs untouched.  src_f16 = dst_f16 = 0: the twin itself. */
+int pnnp_image_fits_es(int H, int W, int cstride, int elem_bytes /*2 or 4*/);
+/* MaxPool2d(2) of an fp16 NHWC map (a pooled layer that ran split-K has no pool in its epilogue): H, W even, C in multiples of 8, 16-byte aligned */
+int pnnp_maxpool2_fwd_f16(const void* x, void* y, int B, int H, int W, int C, void* stream);
+int pnnp_conv3x3_h1_fwd_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                           const unsigned* amax_w, const float* bias, void* y, unsigned* amax_y /*or null*/, int src_f16, int dst_f16,
+                           int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv3x3_h1_fwd_splitk_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                                  const unsigned* amax_w, const float* bias, void* y, unsigned* amax_y, int src_f16, int dst_f16,
+                                  int B, int H, int W, int Cout, int act, int ksplit, float* ws, int64_t ws_floats, void* stream);
+int pnnp_conv3x3_h1_fwd_head_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                                const unsigned* amax_w, const float* bias, const float* head_w, const float* head_b /*or null*/, const float* head_res /*or null*/,
+                                float* head_out, int src_f16, int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv3x3_h1_fwd_pool_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                                const unsigned* amax_w, const float* bias, void* y, void* pooled, unsigned char* codes, unsigned* amax_y /*or null*/,
+                                int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream);
+/* ConvTranspose2d(k2, s2) in the same sense (pnnp_convt_h1_fwd_f32's contract, kind-8 pack): x and y both fp16 (1, 1) or the twin (0, 0); a mixed pair is
+ * PNNP_E_UNSUPPORTED.  One image of x / y must stay below 2 GB in 2-byte elements. */
+int pnnp_convt_h1_fwd_et(const void* x, int Cin, const unsigned* amax_x /*or null for fp16*/, const void* w_h1, const unsigned* amax_w, const float* bias /*or null*/,
+                         void* y, unsigned* amax_y /*or null*/, int src_f16, int dst_f16, int B, int H, int W, int Cout, void* stream);
 int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, const unsigned* bits1, int mode1, int accum1, unsigned* amax_dx1,
                                  float* dx2 /*or null*/, int C2, const float* mask2, const unsigned* bits2, int mode2, int accum2, unsigned* amax_dx2,

@@ -60,7 +60,7 @@ class _EngineBase:
         if policy is None:
             cur = dict(wino=self.policy.wino, wino_wgrad=self.policy.wino_wgrad, wino_mink=self.policy.wino_mink, x3=self.policy.x3,
                        thin=self.policy.thin, pool_fused=self.policy.pool_fused, h2=self.policy.h2)
-            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval', 'h1_pointwise'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
+            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval', 'h1_pointwise', 'h1_act16'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
                 if k in kw:
                     self._h2_sub[k] = bool(kw.pop(k))
             if 'unpool_levels' in kw:                              # which encoder levels unpool_fused applies to (plan.py)
@@ -82,7 +82,15 @@ class _EngineBase:
         per image (pnnp_x3_image_fits; ~16.7 M pixels at nf = 32).  A larger frame is refused HERE, before anything is packed or
         launched, instead of failing with PNNP_E_UNSUPPORTED somewhere inside the network: tile the frame.  (The batch-wide limit of
         the bf16x3 backward-weight kernel is different: past it the layer falls back to the fp32 kernels: plan.py.)"""
+        self._needs_act16 = False
         if not ops.x3_image_fits(H, W, cs_max):
+            # fp16 storage (Plan.act16): the conv / pooled / up-sampled maps are 2-byte tensors, so THEIR bound doubles (~33 M pixels at nf = 32); x8 and the
+            # padded output keep the 4-byte one.  Whether this forward's plan has fp16 storage is known once it is resolved: _forward_begin refuses then.
+            pol = self.policy
+            if (pol.h1_eval and pol.h1_pointwise and pol.h1_act16 and ops.image_fits(H, W, cs_max, 2)
+                    and ops.image_fits(H, W, max(self.cin_pad, self.cout_pad), 4)):
+                self._needs_act16 = True
+                return pol
             raise PnnpError(f'frame {H} x {W} is too large for the HIP convolution kernels: one image of a {cs_max}-channel map must stay '
                             f'below 2 GB ((H + 4) * W * {cs_max} * 4 bytes); run the frame in tiles: evaluate(..., tiles=dict(patch_size=...)) / '
                             f'forward_tiled (pnnp_amd/evaluate.py)')
@@ -295,6 +303,9 @@ class _EngineBase:
         # packed weights are re-used while no parameter changed (eval loops); in-place torch updates bump
         # tensor._version, the fused Adam kernel goes through mark_dirty()
         plan = self._plan = self._plan_for(B, H, W, train)
+        if self._needs_act16 and not plan.act16:
+            raise PnnpError(f'frame {H} x {W} is too large for float32 activation maps (one image of a map must stay below 2 GB) and this forward has no fp16 '
+                            f'storage (ConvPolicy.h1_act16 takes effect in UNet eval plans whose layers all run on fp16x1): run the frame in tiles (forward_tiled)')
         self._packs_ready(train, dev, plan)
         key = (B, H, W, dev)
         self._begin_forward(key, train)
@@ -316,7 +327,21 @@ class _EngineBase:
         ops.tile_crop(x, grid, t0, nt, nchw=xt, nhwc=x8, amax=amax)
         return x8, xt
 
+    def act16_range(self):
+        """Debug aid for the ONE caveat of fp16 activation storage (Plan.act16): a stored map is float16(y), unscaled and not saturated, so
+        |y| > 65504 becomes inf.  Per stored map of the last eval forward that ran with fp16 storage: ``dict(name, amax, overflow)``, amax = max |y| of the
+        float32 values BEFORE the rounding (the layers' amax slots), overflow = 65504 < amax < inf: THIS layer computed finite values that fp16 cannot hold;
+        ``inherited`` = amax is inf (a map downstream of an overflow: it read the inf).  Synchronises; never on the forward path."""
+        if getattr(self, '_act16_last', None) is None:
+            raise PnnpError('act16_range: no eval forward with fp16 activation storage has run (ConvPolicy.h1_act16, Plan.act16)')
+        names, slots = self._act16_last
+        vals = torch.stack([s.reshape(()) for s in slots]).cpu().view(torch.float32).tolist()
+        return [dict(name=n, amax=v, overflow=65504.0 < v < float('inf'), inherited=v == float('inf')) for n, v in zip(names, vals)]
+
     def _forward_end(self, a, key, plan, T):
+        if plan.act16:                         # the stored fp16 maps' slots, by layer (conv9_2's map is never stored: the head is in its epilogue)
+            names = [n for n in plan.steps if n not in ('conv9_2', 'conv10_1')]
+            self._act16_last = (names, [T.slot(n) for n in names])
         if plan.train:
             a['_plan'] = plan
             a['_src_name'] = T.names
@@ -368,6 +393,14 @@ class _EngineBase:
         s, (f, _, wslot) = plan[name], self._wp[name]
         fam, var = self._fam(s.fwd)
         f16 = fam in ('h2', 'h1')                            # both fp16 families: one arm, the family picks the ops wrapper (h1: eval plans only)
+        if plan.act16:                                       # fp16 storage: every layer is 'h1...'; the element types are the tensors' dtypes (x8 alone is float32)
+            assert residual is None and fill is None, 'an fp16-storage plan has no residual layer and every source comes with its slot'
+            ax1 = T.of(x1) if x1.dtype == torch.float32 else None
+            if var == 'splitk':
+                ops.conv_h1a_fwd_splitk(x1, x2, f, wslot, bias, y, cout, act, s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev), amax_x1=ax1, amax_y=T.slot(name))
+            else:
+                ops.conv_h1a_fwd(x1, x2, f, wslot, bias, y, cout, act, amax_x1=ax1, amax_y=T.slot(name))
+            return T.put(y, name, fused=True)
         if f16:
             bits = self._bits(plan, name, T, a, y, cout, act) if fam == 'h2' and residual is None else None      # sign bits: fp16x2 only
             if fill is not None:
@@ -399,6 +432,14 @@ class _EngineBase:
         """a 3x3 layer and the MaxPool2d(2) behind it: y, pooled and (if not None) the argmax + sign codes"""
         s, (f, _, wslot) = plan[name], self._wp[name]
         fam, var = self._fam(s.fwd)
+        if plan.act16:
+            if var == 'pool':
+                ops.conv_h1a_fwd_pool(x, None, f, wslot, bias, y, pooled, codes, cout, act, amax_y=T.slot(name))
+                T.put(y, name, fused=True)
+            else:                              # (a split-K launch has no pool in its epilogue)
+                self._conv3_fwd(plan, name, T, a, x, None, bias, y, cout, act)
+                ops.maxpool_fwd_f16(y, pooled)
+            return y
         if var == 'pool' and fam in ('h2', 'h1'):
             # the layer writes the pooled map, the codes, its amax (the pooled map is a subset) and (fp16x2) the sign bits from its own epilogue
             self._op(f'conv_{fam}_fwd_pool')(x, None, f, wslot, bias, y, pooled, codes, cout, act, T.of(x), amax_y=T.slot(name),
@@ -424,6 +465,9 @@ class _EngineBase:
         # 3x3 layer's map is stored (with its sign bits and amax) only for a backward pass -- an eval forward neither writes nor re-reads it
         f, _, wslot = self._wp[name]
         fam = self._fam(plan[name].fwd)[0]
+        if plan.act16:                         # fp16 source, float32 NCHW out, nothing else stored
+            ops.conv_h1a_fwd_head(x, None, f, wslot, bias, yshape[3], act, hw, hb, out, residual=res)
+            return None
         y = T.bufs.get(name, yshape, T.dev) if plan.train else None
         self._op(f'conv_{fam}_fwd_head')(x, None, f, wslot, bias, y, yshape[3], act, T.of(x), hw, hb, out, amax_y=T.slot(name) if plan.train else None,
                                          bits_y=self._bits(plan, name, T, a, y, yshape[3], act) if fam == 'h2' else None, residual=res)
@@ -569,6 +613,9 @@ class _EngineBase:
     def _convt_fwd(self, plan, name, T, x, bias, y, cout):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
+        if plan.act16:
+            ops.convt_h1a_fwd(x, f, wslot, bias, y, cout, amax_y=T.slot(name))
+            return T.put(y, name, fused=True)
         if fam in ('h2', 'h1'):
             self._op(f'convt_{fam}_fwd')(x, T.of(x), f, wslot, bias, y, cout, amax_y=T.slot(name))
         elif fam == 'x3':
@@ -679,10 +726,13 @@ class _Bufs:
     def __init__(self):
         self.t = {}
 
-    def get(self, name, shape, device):
+    def get(self, name, shape, device, dtype=torch.float32):
+        """(an fp16 map of an fp16-storage eval forward -- Plan.act16 -- is keyed apart from the float32 buffer of the same layer)"""
+        if dtype != torch.float32:
+            name = f'{name}:{str(dtype).split(".")[-1]}'
         b = self.t.get(name)
         if b is None or tuple(b.shape) != tuple(shape) or b.device != device:
-            b = torch.empty(shape, dtype=torch.float32, device=device)
+            b = torch.empty(shape, dtype=dtype, device=device)
             self.t[name] = b
         return b
 

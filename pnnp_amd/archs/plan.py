@@ -51,13 +51,17 @@ class ConvPolicy:
         # (opt-in, off by default) ... and, with ``h1_eval``, the ConvTranspose2d / 1x1 / stride-2 layers that are on the pointwise fp16x2 kernel as well
         # (csrc/gemm_h1s.hip: one matrix instruction per 32 channels where fp16x2 issues three).  Without ``h2`` and ``h1_eval`` it changes nothing.
         self.h1_pointwise = bool(h2) and os.environ.get('PNNP_H1_POINTWISE', '0') != '0'
+        # (opt-in, off by default) ... and, with BOTH, every map a convolution writes and a convolution reads is STORED as fp16 in a UNet eval forward whose
+        # layers all resolved to 'h1...' / 'fused' (Plan.act16; csrc/conv_h1s.hip H1a, csrc/gemm_h1s.hip H1ga): float16(y) of the float32 value, unscaled, not
+        # saturated.  In every other case -- ResUnet, a layer held on another family, a training plan -- it changes nothing.
+        self.h1_act16 = bool(h2) and os.environ.get('PNNP_H1_ACT16', '0') != '0'
 
     def key(self):
         return (self.wino, self.wino_wgrad, self.wino_mink, self.x3, self.thin, self.pool_fused, self.h2, self.h2_wgrad, self.h2_pointwise, self.head_fused, self.splitk, self.convt_bits)
 
     def plan_key(self):
         """What a cached Plan depends on: key() (the families and packs) + the switches that only change the launch sequence."""
-        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval, self.h1_pointwise)
+        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval, self.h1_pointwise, self.h1_act16)
 
     def use_thin_head(self, cin, cout, npix):
         return self.thin and ops.head_supported(cin, cout, npix)
@@ -134,6 +138,7 @@ class Plan:
     def __init__(self, steps, pol, train, ws):
         self.steps, self.pol, self.train, self.ws = steps, pol, train, ws
         self.h2 = any(p == 'h2' for s in steps.values() for p in s.pack)
+        self.act16 = False                  # (UNet eval plans under ConvPolicy.h1_act16) conv, pooled and up-sampled maps are stored as fp16: mark_act16()
         # the weight packs the engines build; they depend on the policy and the mode only, never on B, H, W
         self.packs = tuple(s.pack for s in steps.values())
 
@@ -151,6 +156,13 @@ class Plan:
             if s.fwd in ('h2', 'h2+pool', 'h2+splitk', 'h2+head'):
                 s.fwd, s.pack = 'h1' + s.fwd[2:], ('h1', s.pack[1])
         self.packs = tuple(s.pack for s in self.steps.values())
+        return self
+
+    def mark_act16(self):
+        """(eval plans, ConvPolicy.h1_eval + h1_pointwise + h1_act16) fp16 storage of the activations, if EVERY layer's forward is an fp16x1 launch ('h1...', or
+        'fused' into one): a map has one element type, so one layer on another family keeps the whole plan on float32 storage -- the fp16_all plan, unchanged.
+        The launch sequence is the same either way: families, variants and K slices stay."""
+        self.act16 = not self.train and all(s.fwd == 'fused' or s.fwd.split('+')[0] == 'h1' for s in self.steps.values())
         return self
 
     # (kind, K, N) of a pointwise forward GEMM that stays on fp16x2 under h1_pointwise because one piece measured SLOWER there (none so far)
@@ -246,6 +258,8 @@ def resolve_unet(ch, cin, cout, pol, train, B, H, W):
         plan.to_h1([f'conv{i}_{j}' for i in range(1, 10) for j in (1, 2)])
         if pol.h1_pointwise:
             plan.to_h1_pointwise({f'upv{i}': ('convt', ch[10 - i], 4 * ch[9 - i]) for i in range(6, 10)})
+            if pol.h1_act16:
+                plan.mark_act16()
     if train:
         for i in range(6, 10):             # the skip gradient of conv{i}_1 + MaxPool2d backward in one epilogue: needs the skip tensor's sign bits and codes
             skip = st[f'conv{10 - i}_2']

@@ -59,17 +59,19 @@ class UNetEngine(_EngineBase):
         ch = self.ch
         g = lambda n, s: bufs.get(n, s, dev)
         a = {}
+        # (Plan.act16: conv, pooled and up-sampled maps are fp16 buffers, keyed apart from the float32 ones; x8, the split-K slabs and the output stay float32)
+        gm = (lambda n, s: bufs.get(n, s, dev, torch.float16)) if plan.act16 else g
         # the zero-padded NHWC copy of the network input; its amax rides on the layout pass when conv1_1 runs on the fp16x2 kernel.  (A pooled
         # map shares its full-resolution map's amax slot.)
         x8, x = self._layout_in(x, g('x8', (B, H, W, self.cin_pad)), reflect_pad, self._in_amax(plan, 'conv1_1', T), tile_src, bufs, dev)
         a['x8'] = T.put(x8, 'x8', True)
 
         def conv(name, src, src2, h, w, cout):
-            return self._conv3_fwd(plan, name, T, a, src, src2, P[name + '.bias'], g(name, (B, h, w, cout)), cout, LRELU)
+            return self._conv3_fwd(plan, name, T, a, src, src2, P[name + '.bias'], gm(name, (B, h, w, cout)), cout, LRELU)
 
         hs = [H >> i for i in range(5)]
         ws = [W >> i for i in range(5)]
-        cur = a['c1a'] = self._first_fwd(plan, 'conv1_1', T, a, a['x8'], P['conv1_1.weight'], P['conv1_1.bias'], g('conv1_1', (B, H, W, ch[0])), ch[0], LRELU)
+        cur = a['c1a'] = self._first_fwd(plan, 'conv1_1', T, a, a['x8'], P['conv1_1.weight'], P['conv1_1.bias'], gm('conv1_1', (B, H, W, ch[0])), ch[0], LRELU)
         for lvl in range(5):               # encoder: conv{l}_1, conv{l}_2, pool
             i = lvl + 1
             if i > 1:
@@ -85,13 +87,13 @@ class UNetEngine(_EngineBase):
                 if codes is None or tuple(codes.shape) != shp or codes.device != dev:
                     codes = bufs.t[f'pc{i}'] = torch.empty(shp, dtype=torch.uint8, device=dev)
                 a[f'pc{i}'] = codes
-            pooled = g(f'p{i}', shp)
-            a[f'c{i}'] = self._conv3_pool_fwd(plan, name, T, a, a[f'c{i}a'], P[name + '.bias'], g(name, (B, hs[lvl], ws[lvl], ch[lvl])), pooled, codes, ch[lvl], LRELU)
+            pooled = gm(f'p{i}', shp)
+            a[f'c{i}'] = self._conv3_pool_fwd(plan, name, T, a, a[f'c{i}a'], P[name + '.bias'], gm(name, (B, hs[lvl], ws[lvl], ch[lvl])), pooled, codes, ch[lvl], LRELU)
             a[f'p{i}'] = cur = T.put(pooled, name, fused=True)        # max |pooled| <= max |full-resolution map|
         cur = a['c5']
         for i in range(6, 10):             # decoder: upv{i}, conv{i}_1 on [up, skip], conv{i}_2 (conv9_2: with the head, below)
             lvl = 9 - i
-            u = a[f'u{i}'] = self._convt_fwd(plan, f'upv{i}', T, cur, P[f'upv{i}.bias'], g(f'u{i}', (B, hs[lvl], ws[lvl], ch[lvl])), ch[lvl])
+            u = a[f'u{i}'] = self._convt_fwd(plan, f'upv{i}', T, cur, P[f'upv{i}.bias'], gm(f'u{i}', (B, hs[lvl], ws[lvl], ch[lvl])), ch[lvl])
             a[f'c{i}a'] = conv(f'conv{i}_1', u, a[f'c{lvl + 1}'], hs[lvl], ws[lvl], ch[lvl])
             if i < 9:
                 a[f'c{i}'] = cur = conv(f'conv{i}_2', a[f'c{i}a'], None, hs[lvl], ws[lvl], ch[lvl])

@@ -6,9 +6,10 @@
 int pnnp_igemm_launch(const IgemmArgs& a, int taps, int chan_per_seg, hipStream_t s);
 int pnnp_igemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);       // csrc/conv_x3s.hip (3x3, bf16x3 split)
 int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);        // csrc/gemm_x3.hip (one tap per K segment, bf16x3 split)
-int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg);                        // its argument validation alone
+int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg, int src_es = 4, int dst_es = 4);      // its argument validation alone (element sizes: 2 for fp16 maps)
 int pnnp_gemm_h2s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h2s.hip (the same GEMMs on the fp16x2 scheme; both: the kernel of csrc/gemm_s.h)
 int pnnp_gemm_h1s_launch(const H2Args& a, hipStream_t s);                             // csrc/gemm_h1s.hip (... on the fp16x1 scheme: eval forward only)
+int pnnp_gemm_h1a_launch(const H2Args& a, hipStream_t s);                             // ... with fp16 activations on both sides
 
 namespace {
 
@@ -119,9 +120,16 @@ struct F16Family {
     int (*pointwise)(const H2Args&, hipStream_t);        // the pointwise launcher
     int pack_bytes;                                      // of one 32-column block x 32-channel item of a pointwise pack
     bool sign_bits;                                      // a 3x3 forward may write the sign bits of its activated output
+    bool dst_f16;                                        // the destination (and the pooled map) is an fp16 tensor behind the float* of the bodies below
+    bool src_f16;                                        // ... and so are the K segments: they have no amax slots
 };
-const F16Family FAM_H2{pnnp_igemm_h2s_launch, pnnp_gemm_h2s_launch, 4096, true};
-const F16Family FAM_H1{pnnp_igemm_h1s_launch, pnnp_gemm_h1s_launch, 2048, false};
+const F16Family FAM_H2{pnnp_igemm_h2s_launch, pnnp_gemm_h2s_launch, 4096, true, false, false};
+const F16Family FAM_H1{pnnp_igemm_h1s_launch, pnnp_gemm_h1s_launch, 2048, false, false, false};
+// fp16x1 with fp16 activations on the source and / or destination side (csrc/conv_h1s.hip H1a): [src_f16][dst_f16].  The bodies below carry such a tensor as
+// the float* it is not; only the launcher dereferences it.  (A split-K launch writes float32 slabs whatever the final destination is.)
+template <int S16, int D16> int conv3_h1a(const H2Args& a, int cps, hipStream_t s) { return pnnp_igemm_h1a_launch(a, cps, S16, a.ksplit > 1 ? 0 : D16, s); }
+const F16Family FAM_H1A[2][2] = {{FAM_H1, {conv3_h1a<0, 1>, nullptr, 2048, false, true, false}},
+                                 {{conv3_h1a<1, 0>, nullptr, 2048, false, false, true}, {conv3_h1a<1, 1>, pnnp_gemm_h1a_launch, 2048, false, true, true}}};
 
 // the amax slots of a launch (csrc/h2.h): K segments 0 / 1 (in1 null without a second segment), the weight pack, destination 0 -- which the 3x3 kernels
 // take from H2Args and the pointwise kernels from the IgemmArgs inside it (where their bf16x3 twin reports it)
@@ -159,6 +167,7 @@ int conv3_fwd_splitk(const F16Family& f, const float* x1, int C1, const unsigned
     a.ksplit = ksplit;
     const int rc = f.conv3(a, C1, as_stream(stream));
     if (rc != PNNP_OK) return rc;
+    if (f.dst_f16) return pnnp_h1_splitk_reduce_f16_launch(ws, ksplit, bias, y, amax_y, B, H, W, Cout, act, as_stream(stream));
     return pnnp_h2_splitk_reduce_launch(ws, ksplit, bias, y, bits_y, amax_y, B, H, W, Cout, act, as_stream(stream));
 }
 
@@ -191,7 +200,7 @@ int conv3_fwd_pool(const F16Family& f, const float* x1, int C1, const unsigned* 
 
 // a pointwise launch of either family: K (channels of a segment) and N (GEMM columns) in multiples of 32 (pnnp_gemm_h2_supported)
 int gemm_f16_go(const F16Family& f, H2Args& h, int chan_per_seg, hipStream_t st) {
-    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg);
+    const int rc = pnnp_gemm_x3_check(h.g, chan_per_seg, f.src_f16 ? 2 : 4, f.dst_f16 ? 2 : 4);
     if (rc != PNNP_OK) return rc;
     if (!pnnp_gemm_h2_supported(chan_per_seg, h.g.Ntot)) return PNNP_E_UNSUPPORTED;
     h.g.seg_channels = chan_per_seg;
@@ -202,7 +211,7 @@ int gemm_f16_go(const F16Family& f, H2Args& h, int chan_per_seg, hipStream_t st)
 
 int convt_fwd(const F16Family& f, const float* x, int Cin, const unsigned* amax_x, const void* w, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
               int B, int H, int W, int Cout, void* stream) {
-    if (!x || !w || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;
+    if (!x || !w || !y || (!amax_x && !f.src_f16) || !amax_w || !f.pointwise || B < 0 || H <= 0 || W <= 0) return PNNP_E_INVALID;      // (an fp16 source has no slot)
     if (B == 0) return PNNP_OK;
     H2Args h{};
     convt_fwd_args(h.g, x, Cin, w, bias, y, B, H, W, Cout);
@@ -310,6 +319,11 @@ int pnnp_x3_image_fits(int H, int W, int cstride) {
     return (H > 0 && W > 0 && cstride > 0 && ((int64_t)H + 4) * W * cstride * 4 < (1ll << 31)) ? 1 : 0;
 }
 
+// ... the same question for a map of `elem_bytes`-byte elements (2: an fp16 activation of the fp16x1 family, csrc/conv_h1s.hip H1a; 4: pnnp_x3_image_fits)
+int pnnp_image_fits_es(int H, int W, int cstride, int elem_bytes) {
+    return ((elem_bytes == 2 || elem_bytes == 4) && H > 0 && W > 0 && cstride > 0 && ((int64_t)H + 4) * W * cstride * elem_bytes < (1ll << 31)) ? 1 : 0;
+}
+
 int pnnp_conv3x3_x3_fwd_f32(const float* x1, int C1, const float* x2, int C2, const void* w_x3, const float* bias,
                             const float* residual, float* y, int B, int H, int W, int Cout, int act, void* stream) {
     if (!x1 || !w_x3 || !y || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
@@ -409,6 +423,39 @@ int pnnp_conv3x3_h1_fwd_head_f32(const float* x1, int C1, const unsigned* amax_x
 int pnnp_conv3x3_h1_fwd_pool_f32(const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
                                  const float* bias, float* y, float* pooled, unsigned char* codes, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
     return conv3_fwd_pool(FAM_H1, x1, C1, amax_x1, x2, C2, amax_x2, w_h1, amax_w, bias, y, pooled, codes, amax_y, nullptr, B, H, W, Cout, act, stream);
+}
+
+// ---------------------------------------------------------------- ... with fp16 ACTIVATIONS (csrc/conv_h1s.hip H1a): src_f16: x1 / x2 are fp16 NHWC tensors, taken as they
+// are (unscaled: their amax slots are not read and may be null); dst_f16: y (and the pooled map) are fp16 = float16(the float32 value the entry above stores), amax_y
+// still max |.| of the float32 value.  The same bodies; src_f16 = dst_f16 = 0 is the entry above.  No residual; the head entry stores no 32-channel map.
+int pnnp_conv3x3_h1_fwd_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                           const float* bias, void* y, unsigned* amax_y, int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream) {
+    return conv3_fwd(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, nullptr, (float*)y, amax_y, nullptr,
+                     B, H, W, Cout, act, stream);
+}
+int pnnp_conv3x3_h1_fwd_splitk_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                                  const float* bias, void* y, unsigned* amax_y, int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, int ksplit, float* ws,
+                                  int64_t ws_floats, void* stream) {
+    return conv3_fwd_splitk(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, (float*)y, amax_y, nullptr,
+                            B, H, W, Cout, act, ksplit, ws, ws_floats, stream);
+}
+int pnnp_conv3x3_h1_fwd_head_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                                const float* bias, const float* head_w, const float* head_b, const float* head_res, float* head_out, int src_f16, int B, int H, int W,
+                                int Cout, int act, void* stream) {
+    return conv3_fwd_head(FAM_H1A[!!src_f16][0], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, nullptr, nullptr, nullptr, head_w, head_b,
+                          head_res, head_out, B, H, W, Cout, act, stream);
+}
+// ConvTranspose2d(k2, s2) of an fp16-storage forward: x and y fp16 (src_f16 = dst_f16 = 1), or the _f32 twin (both 0); a mixed pair: PNNP_E_UNSUPPORTED
+int pnnp_convt_h1_fwd_et(const void* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, void* y, unsigned* amax_y,
+                         int src_f16, int dst_f16, int B, int H, int W, int Cout, void* stream) {
+    if (!src_f16 != !dst_f16) return PNNP_E_UNSUPPORTED;
+    return convt_fwd(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x, Cin, amax_x, w_h1, amax_w, bias, (float*)y, amax_y, B, H, W, Cout, stream);
+}
+int pnnp_conv3x3_h1_fwd_pool_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                                const float* bias, void* y, void* pooled, unsigned char* codes, unsigned* amax_y, int src_f16, int dst_f16, int B, int H, int W, int Cout,
+                                int act, void* stream) {
+    return conv3_fwd_pool(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, (float*)y, (float*)pooled, codes,
+                          amax_y, nullptr, B, H, W, Cout, act, stream);
 }
 
 // mask1 / mask2: the float32 activation, or bits1 / bits2: its sign bits from the forward kernel (then the float32 pointer is not read)

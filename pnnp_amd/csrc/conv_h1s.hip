@@ -96,7 +96,105 @@ igemm_h1s_kernel(const H2Args ha) {
 template <int BN, int EK>
 int launch_h1s(const H2Args& a, hipStream_t s) { return conv_s_launch<H1s, BN, EK, igemm_h1s_kernel<BN, EK>>(a, s); }
 
+// ---- the same scheme with fp16 ACTIVATIONS on one or both sides ("h1a": csrc/conv_s.h SElem, csrc/conv_s_body.h SRC16 / DST16).  An fp16 source is unscaled
+// (se_x = 0: its halves are the halo image's words, dexp = -se_w) and has no amax slot; an fp16 destination is float16(y) of the float32 value H1s stores, and
+// its amax slot still records max |y| BEFORE the rounding.  Same pack (kind 7), same mfma_item: fed x16 and x16.float() the two schemes add the same products
+// times the same power of two in the same order.  Split-K slabs (EK_GEN) stay float32; the residual epilogue is not offered.
+template <bool S16, bool D16>
+struct H1a : H1s {
+    static constexpr bool SRC16 = S16, DST16 = D16;
+    static constexpr bool has(int EK, int BN) { return D16 ? (EK == EK_FWD || EK == EK_POOL) : (EK == EK_FWD || EK == EK_GEN || (EK == EK_HEAD && BN == 32)); }
+    static __device__ __forceinline__ void scale_exps(const H2Args& ha, int& se_x, int& se_w) {
+        if constexpr (S16) { se_x = 0; se_w = __builtin_amdgcn_readfirstlane(ha.amax_w ? pnnp_h2_scale_exp(ha.amax_w[0]) : 0); }
+        else H1s::scale_exps(ha, se_x, se_w);
+    }
+};
+
+template <int BN, int EK, bool S16, bool D16>
+__global__ void __launch_bounds__(NTHR, 1)
+igemm_h1a_kernel(const H2Args ha) {
+    using Scheme = std::enable_if_t<BN != 0, H1a<S16, D16>>;
+#include "conv_s_body.h"
+}
+
+template <int BN, int EK, bool S16, bool D16>
+int launch_h1a(const H2Args& a, hipStream_t s) { return conv_s_launch<H1a<S16, D16>, BN, EK, igemm_h1a_kernel<BN, EK, S16, D16>>(a, s); }
+
+// h2_splitk_reduce_kernel (csrc/conv_h2s.hip) with an fp16 destination: the same float32 sums in the same order, bias, activation, max |.| of the float32
+// value, then one rounding; 4 channels = 8 bytes per thread.  No sign bits (an eval forward).
+__global__ void __launch_bounds__(256)
+h1_splitk_reduce_f16_kernel(const float* __restrict__ slab, int S, const float* __restrict__ bias, _Float16* __restrict__ y, unsigned* __restrict__ amax, int64_t img, int N, int act) {
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    const int nq = N >> 2;
+    const int64_t total = img >> 2, st4 = img >> 2;
+    const float slope = act == 1 ? 0.2f : (act == 2 ? 0.f : 1.f);
+    float am = 0.f;
+    for (int64_t e4 = (int64_t)blockIdx.x * 256 + threadIdx.x; e4 < total; e4 += (int64_t)gridDim.x * 256) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(slab) + e4;
+        f32x4 o = p[0];
+        int sidx = 1;
+        for (; sidx + 3 < S; sidx += 4) {
+            const f32x4 v0 = p[sidx * st4], v1 = p[(sidx + 1) * st4], v2 = p[(sidx + 2) * st4], v3 = p[(sidx + 3) * st4];
+            o += v0; o += v1; o += v2; o += v3;
+        }
+        for (; sidx < S; ++sidx) o += p[sidx * st4];
+        const int ch = (int)(e4 % nq) * 4;
+        if (bias) o += *reinterpret_cast<const f32x4*>(bias + ch);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = o[c] > 0.f ? o[c] : o[c] * slope;
+        reinterpret_cast<f16x4*>(y)[e4] = f16x4{(_Float16)o.x, (_Float16)o.y, (_Float16)o.z, (_Float16)o.w};
+        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    }
+    if (amax) pnnp_amax_commit_block(am, amax);
+}
+
 }  // namespace
+
+int pnnp_h1_splitk_reduce_f16_launch(const float* slab, int S, const float* bias, void* y, unsigned* amax, int B, int H, int W, int N, int act, hipStream_t st) {
+    const int64_t img = (int64_t)B * H * W * N, total = img / 4;
+    if (total <= 0) return PNNP_OK;
+    const int64_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(h1_splitk_reduce_f16_kernel, dim3((unsigned)(blocks > 256 ? 256 : blocks)), dim3(256), 0, st, slab, S, bias, static_cast<_Float16*>(y), amax, img, N, act);
+    return pnnp_launch_status();
+}
+
+// pnnp_igemm_h1s_launch with element types: src_f16: every K segment is an fp16 NHWC tensor (a.seg[i].ptr points at halves; cstride and coff in multiples of 8,
+// no amax slot read); dst_f16: dst[0] and the pooled map are fp16 (channel strides in multiples of 8).  Refuses what pnnp_igemm_h1s_launch refuses, and: a
+// residual, an fp16 split-K slab, a stored map beside the head.  Both zero: pnnp_igemm_h1s_launch itself.
+int pnnp_igemm_h1a_launch(const H2Args& ha, int chan_per_seg, int src_f16, int dst_f16, hipStream_t s) {
+    if (!src_f16 && !dst_f16) return pnnp_igemm_h1s_launch(ha, chan_per_seg, s);
+    const IgemmArgs& a = ha.g;
+    H2Args b = ha;
+    if (!ha.amax_w || (!src_f16 && (!ha.amax_in[0] || (a.nseg > 1 && !ha.amax_in[1])))) return PNNP_E_INVALID;
+    if (src_f16) { b.amax_in[0] = nullptr; b.amax_in[1] = nullptr; }
+    if ((((uintptr_t)b.amax_in[0]) | ((uintptr_t)b.amax_in[1]) | ((uintptr_t)ha.amax_w) | ((uintptr_t)ha.amax_out[0]) | ((uintptr_t)ha.amax_out[1])) & 3) return PNNP_E_INVALID;
+    if (a.mask[0] || a.mask[1] || a.mask_mode[0] || a.mask_mode[1] || a.accum[0] || a.accum[1] || ha.bits_out || ha.bits_in[0] || ha.bits_in[1] ||
+        ha.unpool_g || ha.unpool_codes || ha.dgrad_plain || a.addsrc || a.dst[1]) return PNNP_E_UNSUPPORTED;
+    if (const int rc = conv_s_validate(a, chan_per_seg, H1s::ITEMS * H1s::WBLK, b.g, src_f16 ? 2 : 4, dst_f16 ? 2 : 4); rc != PNNP_OK) return rc;
+    if (b.ksplit < 1) b.ksplit = 1;
+    if (b.ksplit > 1) {
+        if (!src_f16 || dst_f16) return PNNP_E_UNSUPPORTED;           // (slabs are float32; a float32 source takes pnnp_igemm_h1s_launch)
+        if ((b.g.nseg * b.g.chunks_per_seg) % b.ksplit || a.bias || a.act || a.pool_dst || a.pool_codes || ha.head_out || ha.amax_out[0] || !a.dst[0])
+            return PNNP_E_UNSUPPORTED;
+        return pnnp_conv3_tile_columns(a.B * b.ksplit, a.DH, a.DW, a.Ntot, 0) == 64 ? launch_h1a<64, EK_GEN, true, false>(b, s) : launch_h1a<32, EK_GEN, true, false>(b, s);
+    }
+    if (ha.head_out) {
+        if (!src_f16 || dst_f16 || a.dst[0] || ha.amax_out[0]) return PNNP_E_UNSUPPORTED;      // (fp16 source, float32 NCHW head_out, nothing else stored)
+        if (!ha.head_w || a.Ntot != 32 || a.pool_dst || a.pool_codes || a.OH != a.DH || a.OW != a.DW ||
+            (((uintptr_t)ha.head_w | (uintptr_t)ha.head_out | (uintptr_t)ha.head_res | (uintptr_t)ha.head_b) & 3)) return PNNP_E_UNSUPPORTED;
+        return launch_h1a<32, EK_HEAD, true, false>(b, s);
+    }
+    if (!a.dst[0]) return PNNP_E_INVALID;
+    if (a.pool_dst || a.pool_codes) {
+        if (!src_f16 || !dst_f16) return PNNP_E_UNSUPPORTED;          // (the pooled layers of an fp16-storage forward read and write fp16)
+        if (conv_s_validate_pool(a, a.pool_dst, a.pool_codes, 2) != PNNP_OK) return PNNP_E_UNSUPPORTED;
+        return pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 1) == 64 ? launch_h1a<64, EK_POOL, true, true>(b, s) : launch_h1a<32, EK_POOL, true, true>(b, s);
+    }
+    const bool wide = pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 0) == 64;
+    if (src_f16 && dst_f16) return wide ? launch_h1a<64, EK_FWD, true, true>(b, s) : launch_h1a<32, EK_FWD, true, true>(b, s);
+    if (src_f16) return wide ? launch_h1a<64, EK_FWD, true, false>(b, s) : launch_h1a<32, EK_FWD, true, false>(b, s);
+    return wide ? launch_h1a<64, EK_FWD, false, true>(b, s) : launch_h1a<32, EK_FWD, false, true>(b, s);
+}
 
 // pnnp_igemm_h2s_launch restricted to what an eval forward launches.  a.g.w: the one-piece pack of csrc/pack_jobs.hip (kind 7).  Anything with a mask, a bit
 // image, an accumulating destination, an un-pool term or the plain backward-data switch: PNNP_E_UNSUPPORTED.

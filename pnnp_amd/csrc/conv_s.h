@@ -72,6 +72,12 @@ enum { EK_FWD = 0, EK_BWD = 1, EK_GEN = 2, EK_POOL = 3, EK_BWDB = 4, EK_HEAD = 5
 // and written as the NCHW output planes (+ the `res` networks' input residual).  The 32-channel map itself is stored only when the caller asks for it
 // (a training forward: backward needs it); an eval forward never writes or re-reads it.
 
+// Element types of the activations (csrc/conv_h1s.hip H1a): a scheme with SRC16 reads its K segments as fp16 NHWC tensors (one 16-byte load per staging slot,
+// the word goes into the halo image as loaded: no split, no scale), one with DST16 stores dst[0] and the pooled map as fp16 (one round to nearest even of the
+// float32 value the epilogue would store).  A scheme that names neither has float32 on both sides.
+template <class S, class = void> struct SElem { static constexpr bool SRC16 = false, DST16 = false; };
+template <class S> struct SElem<S, std::void_t<decltype(S::SRC16), decltype(S::DST16)>> { static constexpr bool SRC16 = S::SRC16, DST16 = S::DST16; };
+
 constexpr int HEAD_LDS_FLOATS = 256;                               // (EK_HEAD) [4][32] head weights + [4] biases, padded
 template <class Scheme, int BN> struct SCfg {
     static constexpr int NT = BN / 32;
@@ -107,21 +113,25 @@ int conv_s_launch(const H2Args& a, hipStream_t s) {
 // ---- host: what both families' launch entries check before they dispatch.  a.w: the scheme's pack of csrc/pack_jobs.hip (kind 2 / 4), `pack_chunk` bytes per
 // 32-column block and 16-channel chunk.  chan_per_seg: channels each K segment contributes (multiple of 8; of 16 when there are several segments).  Only
 // what the 3x3 / stride-1 layers need: in_mul = out_mul = 1, no sub-pixel N.  PNNP_OK: `b` is `a` with the chunk counts filled in.
-inline int conv_s_validate(const IgemmArgs& a, int chan_per_seg, int pack_chunk, IgemmArgs& b) {
+// src_es / dst_es: bytes per element of the K segments / of dst[0] (2: an fp16 map -- 16-byte words are then 8 channels, and the 2 GB limit of one image is
+// counted in 2-byte elements)
+inline int conv_s_validate(const IgemmArgs& a, int chan_per_seg, int pack_chunk, IgemmArgs& b, int src_es = 4, int dst_es = 4) {
+    const int src_q = 16 / src_es - 1, dst_q = 16 / dst_es - 1;      // channel strides in whole 16-byte words
     if (a.nseg < 1 || a.nseg > 2 || chan_per_seg <= 0 || (chan_per_seg & 7) || (a.nseg > 1 && (chan_per_seg & 15)) || a.Ntot <= 0) return PNNP_E_INVALID;
     if (a.Ntot > 1024) return PNNP_E_UNSUPPORTED;                     // (the bias vector lives in LDS: SCfg::BIAS_MAX columns)
     if ((a.Ntot & 31) || a.in_mul != 1 || a.out_mul != 1 || a.n_sub || a.out_yoff || a.out_xoff) return PNNP_E_UNSUPPORTED;
     if (a.dst[1] && (a.n_split & 31)) return PNNP_E_UNSUPPORTED;
     if (a.addsrc && a.accum[0]) return PNNP_E_UNSUPPORTED;
-    if ((a.dst_cs[0] & 3) || (a.dst[1] && (a.dst_cs[1] & 3))) return PNNP_E_UNSUPPORTED;
+    if ((a.dst_cs[0] & dst_q) || (a.dst[1] && (a.dst_cs[1] & 3))) return PNNP_E_UNSUPPORTED;
+    if (dst_es != 4 && a.dst[1]) return PNNP_E_UNSUPPORTED;
     if ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.bias) | ((uintptr_t)a.mask[0]) | ((uintptr_t)a.mask[1]) |
          ((uintptr_t)a.addsrc) | ((uintptr_t)a.w)) & 15) return PNNP_E_INVALID;
     for (int i = 0; i < a.nseg; ++i) {
-        if (a.seg[i].yoff || a.seg[i].xoff || (a.seg[i].cstride & 3) || (((uintptr_t)a.seg[i].ptr) & 15)) return PNNP_E_UNSUPPORTED;
-        if (((int64_t)a.IH + 4) * a.IW * a.seg[i].cstride * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;     // 32-bit offsets inside one image
+        if (a.seg[i].yoff || a.seg[i].xoff || (a.seg[i].cstride & src_q) || (src_es != 4 && (a.seg[i].coff & src_q)) || (((uintptr_t)a.seg[i].ptr) & 15)) return PNNP_E_UNSUPPORTED;
+        if (((int64_t)a.IH + 4) * a.IW * a.seg[i].cstride * src_es >= (1ll << 31)) return PNNP_E_UNSUPPORTED;     // 32-bit offsets inside one image
     }
     for (int d = 0; d < 2; ++d)
-        if (a.dst[d] && (int64_t)a.OH * a.OW * a.dst_cs[d] * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+        if (a.dst[d] && (int64_t)a.OH * a.OW * a.dst_cs[d] * (d ? 4 : dst_es) >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     b = a;
     b.chunks_per_seg = (chan_per_seg + 15) / 16;
     b.seg_channels = chan_per_seg;
@@ -130,11 +140,11 @@ inline int conv_s_validate(const IgemmArgs& a, int chan_per_seg, int pack_chunk,
 }
 // ... and of a launch with a MaxPool2d(2) in its epilogue, forward (the pooled map and the codes are written) or backward-data (EK_BWDU: the pooled map's
 // gradient and the codes are read): one destination, no residual / accumulation, even sizes, the whole map
-inline int conv_s_validate_pool(const IgemmArgs& a, const void* map, const void* codes) {
-    if (!map || !codes || a.dst[1] || a.accum[0] || a.addsrc || (a.OH & 1) || (a.OW & 1) || a.OH != a.DH || a.OW != a.DW || (a.pool_cs & 3) ||
+inline int conv_s_validate_pool(const IgemmArgs& a, const void* map, const void* codes, int es = 4) {
+    if (!map || !codes || a.dst[1] || a.accum[0] || a.addsrc || (a.OH & 1) || (a.OW & 1) || a.OH != a.DH || a.OW != a.DW || (a.pool_cs & (16 / es - 1)) ||
         a.pool_cs < a.Ntot || ((uintptr_t)map & 15) || ((uintptr_t)codes & 3))
         return PNNP_E_UNSUPPORTED;
-    if ((int64_t)(a.OH / 2) * (a.OW / 2) * a.pool_cs * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+    if ((int64_t)(a.OH / 2) * (a.OW / 2) * a.pool_cs * es >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     return PNNP_OK;
 }
 

@@ -3,6 +3,10 @@
     static_assert(Scheme::has(EK, BN), "an epilogue the scheme's dispatch does not launch");
     const IgemmArgs& a = ha.g;
     constexpr bool POOL = EK == EK_POOL;
+    // element types of the activations (csrc/conv_s.h SElem): fp16 K segments / an fp16 dst[0] and pooled map; LPS: 16-byte loads per staging slot (8 channels)
+    constexpr bool SRC16 = SElem<Scheme>::SRC16, DST16 = SElem<Scheme>::DST16;
+    constexpr int SRC_ES = SRC16 ? 2 : 4, LPS = SRC16 ? 1 : 2;
+    static_assert(!DST16 || EK == EK_FWD || EK == EK_POOL || EK == EK_HEAD, "epilogues with an fp16 destination");
     using Cfg = SCfg<Scheme, BN>;
     constexpr int NT = Cfg::NT, D = Cfg::DPW, XS_F4 = Cfg::XS_F4, XS_BYTES = Cfg::XS_BYTES, NSTAGE = Cfg::NSTAGE, AHEAD = Cfg::AHEAD, ITEMS = Scheme::ITEMS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -110,7 +114,7 @@
             xdst[k] = XS_PLANE(0, oct) + pix;                       // + piece * XS_PIECE_STRIDE (+ image * XS_F4)
         }
         const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-        f32x4 ra[NS][NSLOT][2];                                     // halo chunks in flight / waiting to be split, 8 channels per slot
+        f32x4 ra[NS][NSLOT][LPS];                                   // halo chunks in flight / waiting to be split, 8 channels per slot (SRC16: one word, fp16 as loaded)
         // global loads of the halo tile of (tile, chunk gq) -> register set S: hardware zero for pixels outside the image and channels past the segment
         auto load_halo = [&](auto stag, const Tile& tl, int gq) {
             constexpr int S = decltype(stag)::value;
@@ -120,16 +124,17 @@
             const int c0 = sg.coff + cc * 16;
             const int rlo = -tl.y0, rhi = a.IH - tl.y0, qlo = -tl.x0, qhi = a.IW - tl.x0;
             const int shift = (2 * a.IW + 2) * sg.cstride;         // the resource starts before the image: the scalar offset below stays >= 0
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(sg.ptr + ((int64_t)tl.b * a.IH * a.IW * sg.cstride - shift)), 0, 0x7fffffff, 0x00020000);
-            const int soff = (((tl.y0 - 1) * a.IW + tl.x0 - 1) * sg.cstride + c0 + shift) * 4;
-            const unsigned cs4 = (unsigned)sg.cstride * 4u;
+            const int64_t first = (int64_t)tl.b * a.IH * a.IW * sg.cstride - shift;      // (elements)
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(SRC16 ? (void*)(reinterpret_cast<const _Float16*>(sg.ptr) + first) : (void*)(sg.ptr + first), 0, 0x7fffffff, 0x00020000);
+            const int soff = (((tl.y0 - 1) * a.IW + tl.x0 - 1) * sg.cstride + c0 + shift) * SRC_ES;
+            const unsigned cs4 = (unsigned)sg.cstride * (unsigned)SRC_ES;
             const int cvalid = a.seg_channels - cc * 16 - oct * 8;  // > 0: this thread's octet exists
 #pragma unroll
             for (int k = 0; k < NSLOT; ++k) {
                 const int bad = (rk[k] - rlo) | (rhi - 1 - rk[k]) | (qk[k] - qlo) | (qhi - 1 - qk[k]) | (cvalid - 1);     // sign bit set <=> outside
-                const unsigned vo = bad < 0 ? OOB : __umul24(pixk[k], cs4) + oct * 32;
+                const unsigned vo = bad < 0 ? OOB : __umul24(pixk[k], cs4) + oct * (8 * SRC_ES);
                 ra[S][k][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, soff, 0));
-                ra[S][k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, soff + 16, 0));
+                if constexpr (!SRC16) ra[S][k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, soff + 16, 0));
             }
         };
         // the slots of register set S that work item `item` of a chunk splits -> their PIECES 16-byte words (8 channels of each piece) in halo image img
@@ -138,10 +143,15 @@
             constexpr int K0 = item * Scheme::SLOTS, K1 = item + 1 < ITEMS ? K0 + Scheme::SLOTS : NSLOT;
 #pragma unroll
             for (int k = K0; k < K1; ++k) {
+                if constexpr (SRC16) {                               // the eight halves are the image's word: nothing to split, no scale (se_x = 0)
+                    static_assert(!SRC16 || Scheme::PIECES == 1, "an fp16 source is its own single piece");
+                    xs[img * XS_F4 + xdst[k]] = __builtin_bit_cast(u32x4, ra[S][k][0]);
+                    continue;
+                }
                 u32x4 sp[Scheme::PIECES];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const f32x4 v = ra[S][k][p >> 1];
+                    const f32x4 v = ra[S][k][SRC16 ? 0 : p >> 1];
                     unsigned w[Scheme::PIECES];
                     Scheme::split(v[(p & 1) * 2], v[(p & 1) * 2 + 1], sx, w);
 #pragma unroll
@@ -176,8 +186,8 @@
         //     one (halo loads of an earlier item are not counted: the wait covers them too, and their values are split first anyway);
         //   in front of barrier 0: ALL the prologue's weights (items 0 .. AHEAD - 1), behind them the halos of max(1, NSETS - 1) register sets.
         // bf16x3: BN 32 (AHEAD 2, DPW 3) 3, 3, 3 + 10; BN 64 (AHEAD 1) 0, 0, 10; fp16x2 (AHEAD 1, NSETS 2): 10; barrier 0: 10 each.
-        auto wait_weights = [](auto items_tag, auto sets_tag) { __builtin_amdgcn_s_waitcnt(CS_VMCNT(decltype(items_tag)::value * D + 2 * NSLOT * decltype(sets_tag)::value)); };
-        static_assert((AHEAD - 1) * D + 2 * NSLOT <= 63 && 2 * NSLOT * (NS > 1 ? NS - 1 : 1) <= 63, "the producers' vmcnt");
+        auto wait_weights = [](auto items_tag, auto sets_tag) { __builtin_amdgcn_s_waitcnt(CS_VMCNT(decltype(items_tag)::value * D + LPS * NSLOT * decltype(sets_tag)::value)); };
+        static_assert((AHEAD - 1) * D + LPS * NSLOT <= 63 && LPS * NSLOT * (NS > 1 ? NS - 1 : 1) <= 63, "the producers' vmcnt");
         // ---- prologue: the bias vector, the padding words of the hi planes where the scheme reads them (fp16x2: the unpaired ninth tap's second half reads
         // one pixel past tap 8: word 612 for the last lane of the last row -- multiplied by the pack's zero tap, so it must be FINITE, not whatever bit pattern
         // the LDS held), the weights of items 0 .. AHEAD - 1, chunk 0's halo straight into image 0, the halos of chunks 1 .. max(1, NS - 1) into the register sets
@@ -544,17 +554,44 @@
         auto wo2 = [&](int k, int i, int h) {                    // instruction 2: eight pixels on
             return (wo[k][i][h] != OOB && pxl + 16 * h + 8 < ea.DW) ? wo[k][i][h] + (unsigned)(8 * cs_[k] * 4) : OOB;
         };
+        // ---- (DST16) the same stores with 2-byte channels.  A pixel's 32 channels are 64 bytes, a lane's two quads 8 bytes each: the four lanes of a pixel
+        // (16-lane rows q = 0 .. 3 of the wave) first swap quads so that each holds 8 CONSECUTIVE channels -- v_permlane16_swap: the odd rows of the lower block's
+        // packed quad against the even rows of the upper block's; row q then holds channels 16 (q & 1) + 8 (q >> 1) .. + 7 of its pixel -- and ONE 16-byte store
+        // instruction writes 16 pixels x 64 bytes: 1 KB contiguous where the channel stride is 32, sixteen half lines where it is wider.  The conversion is
+        // one round to nearest even (v_cvt_pk_f16_f32: subnormals kept, no saturation, NaN stays NaN).
+        auto pack16 = [&](f32x4 o0, f32x4 o1) __attribute__((always_inline)) {
+            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+            unsigned a0 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o0.x, (_Float16)o0.y}), a1 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o0.z, (_Float16)o0.w});
+            unsigned b0 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o1.x, (_Float16)o1.y}), b1 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o1.z, (_Float16)o1.w});
+            const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false), s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+            return u32x4{s0[0], s1[0], s0[1], s1[1]};
+        };
+        const int ch16 = ((lane_e >> 4) & 1) * 16 + (lane_e >> 5) * 8;      // first channel (inside a 32-column block) of the lane's word behind the swap
+        unsigned wo16[DST16 ? NT : 1][MT][2];
+        if constexpr (DST16) {
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+                        wo16[k][i][h] = (blk_[k] && okp[i][h]) ? (unsigned)((((py0 + i) * ea.OW + px0 + 16 * h) * cs_[k] + chw_[k] + ch16) * 2) : OOB;
+        }
+        auto rsrc16 = [&](const float* base, int k) {
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const _Float16*>(base) + (int64_t)b * ea.OH * ea.OW * cs_[k]), 0, ea.OH * ea.OW * cs_[k] * 2, 0x00020000);
+        };
         if constexpr (POOL) {
             // Forward layer in front of MaxPool2d(2) (archs/Unet.py:35,41,47,53): single destination, bias + activation only.  A wave owns rows
             // 2w, 2w + 1 of its 32 columns: a lane's two accumulator rows + the same two of lane ^ 1 are one 2x2 window of 4 channels; the even
             // lane writes the pooled float4 and the four codes (bits 0-1 first maximum in the order (0,0) (0,1) (1,0) (1,1), bits 2-5 the signs)
             // of csrc/misc.hip maxpool_fwd_codes_kernel.
             static_assert(MT == 2, "a wave owns one row pair");
-            const __amdgpu_buffer_rsrc_t rd = rsrc(ea.dst(0), 0);
+            const __amdgpu_buffer_rsrc_t rd = DST16 ? rsrc16(ea.dst(0), 0) : rsrc(ea.dst(0), 0);
             const __amdgpu_buffer_rsrc_t rb = bits_rsrc(ea.bits_out, ea.nblk0);
             const int ph = ea.OH >> 1, pwd = ea.OW >> 1;
             const int64_t pimg = (int64_t)b * ph * pwd * ea.pool_cs;
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(ea.pool_dst + pimg), 0, ph * pwd * ea.pool_cs * 4, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rp = DST16 ? __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<_Float16*>(ea.pool_dst) + pimg), 0, ph * pwd * ea.pool_cs * 2, 0x00020000)
+                                                    : __builtin_amdgcn_make_buffer_rsrc((void*)(ea.pool_dst + pimg), 0, ph * pwd * ea.pool_cs * 4, 0x00020000);
             const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(ea.pool_codes + pimg), 0, ph * pwd * ea.pool_cs, 0x00020000);
 #pragma unroll
             for (int k = 0; k < NT; ++k) {
@@ -572,10 +609,15 @@
                         }
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {                     // full resolution: whole lines (the halves of the block pair traded)
+                        if constexpr (DST16) {
+                            __builtin_amdgcn_raw_buffer_store_b128(pack16(wn[0][i], wn[1][i]), rd, wo16[k][i][h], 0, CONVS_STORE_AUX);
+                            continue;
+                        }
                         const f32x4 ox = ror8(sel(lo8, wn[1][i], wn[0][i]));
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sel(lo8, wn[0][i], ox)), rd, wo[k][i][h], 0, CONVS_STORE_AUX);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sel(lo8, ox, wn[1][i])), rd, wo2(k, i, h), 0, CONVS_STORE_AUX);
                     }
+                    f32x4 mx16[DST16 ? 2 : 1];                        // (DST16) the pooled quads of both 16-column blocks: one swapped word per lane
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {
                         const int j = 2 * k + jj;
@@ -609,8 +651,15 @@
                         const int px = px0 + 16 * h;
                         const bool ok2 = !(lane_e & 1) && blk_[k] && py0 < ea.DH && px < ea.DW;      // even sizes: the whole window is inside or outside
                         const unsigned po = (unsigned)(((py0 >> 1) * pwd + (px >> 1)) * ea.pool_cs + n0 + 16 * j + c4);
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, mx), rp, ok2 ? po * 4u : OOB, 0, 0);
+                        if constexpr (DST16) mx16[jj] = mx;
+                        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, mx), rp, ok2 ? po * 4u : OOB, 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b32(code, rc, ok2 ? po : OOB, 0, 0);
+                    }
+                    if constexpr (DST16) {
+                        const int px = px0 + 16 * h;
+                        const bool ok2 = !(lane_e & 1) && blk_[k] && py0 < ea.DH && px < ea.DW;
+                        const unsigned po = (unsigned)(((py0 >> 1) * pwd + (px >> 1)) * ea.pool_cs + n0 + 32 * k + ch16);
+                        __builtin_amdgcn_raw_buffer_store_b128(pack16(mx16[0], mx16[1]), rp, ok2 ? po * 2u : OOB, 0, 0);
                     }
                 }
                 if constexpr (Scheme::BITS) __builtin_amdgcn_raw_buffer_store_b32(sb, rb, (ea.bits_out && blk_[k]) ? bits_off(k, ea.nblk0) : OOB, 0, 0);
@@ -646,7 +695,7 @@
             auto body = [&](auto act_tag) __attribute__((always_inline)) {
 #pragma unroll
                 for (int k = 0; k < NT; ++k) {
-                    const __amdgpu_buffer_rsrc_t rd = rsrc(ea.dst(du_[k]), k);
+                    const __amdgpu_buffer_rsrc_t rd = DST16 ? rsrc16(ea.dst(du_[k]), k) : rsrc(ea.dst(du_[k]), k);
                     const int mm = ea.mask_mode(du_[k]);
                     const float msl = mm == 1 ? 0.2f : (mm == 0 ? 1.f : 0.f);      // act'(x <= 0); a destination without a mask (its requests came back as zeros): 1
                     unsigned sb = 0u;
@@ -725,6 +774,11 @@
                                 }
                                 if (!keep) continue;
                             }
+                            if constexpr (DST16) {
+                                __builtin_amdgcn_raw_buffer_store_b128(pack16(o0, o1), rd, wo16[k][i][h], 0, CONVS_STORE_AUX);
+                                __builtin_amdgcn_sched_barrier(0);      // (one block pair at a time, as the float32 pattern's trade orders them: interleaved, the 64-column kernel spills)
+                                continue;
+                            }
                             trade(o0, o1);
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o0), rd, wo[k][i][h], 0, CONVS_STORE_AUX);
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rd, wo2(k, i, h), 0, CONVS_STORE_AUX);
@@ -765,6 +819,8 @@
             // one wave-uniform branch per tile: with / without an activation (backward-data never has one: the launcher sends a masked layer
             // WITH an activation to the general kernel)
             if constexpr (!FWDL) body(std::false_type{});
+            else if constexpr (DST16) body(std::true_type{});      // (no branch: without an activation the slope is 1 and max(o, 1 o) = o bit for bit.  With two copies
+                                                                    // the compiler hoists their common 64 fma in front of the branch and the 64-column kernel spills)
             else if (ea.act != 0) body(std::true_type{});
             else body(std::false_type{});
             return;

@@ -26,6 +26,7 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 int pnnp_gemm_h1s_launch(const H2Args& a, hipStream_t s);
+int pnnp_gemm_h1a_launch(const H2Args& a, hipStream_t s);
 
 namespace {
 
@@ -62,7 +63,35 @@ int launch_h1g(const H2Args& ha, hipStream_t s) {
     return ha.g.addsrc ? launch_gs<H1g, BN, WN, EK_GEN>(ha, s) : launch_gs<H1g, BN, WN, EK_FWD>(ha, s);
 }
 
+// ---- the same scheme with fp16 ACTIVATIONS on both sides ("h1a": csrc/gemm_s.h GElem): the source's halves are the operands as they are (se_x = 0, no amax slot
+// read), the destination is float16(y) of the float32 value H1g stores, its amax slot still max |y| before the rounding.  Same pack (kind 8), same MFMA order.
+struct H1ga : H1g {
+    static constexpr bool SRC16 = true, DST16 = true;
+    static __device__ __forceinline__ void scale_exps(const H2Args& ha, int& se_x, int& se_w) {
+        se_x = 0; se_w = __builtin_amdgcn_readfirstlane(ha.amax_w ? pnnp_h2_scale_exp(ha.amax_w[0]) : 0);
+    }
+};
+
 }  // namespace
+
+// pnnp_gemm_h1s_launch with fp16 activations on both sides (the up-sampling layers of an fp16-storage eval forward): every K segment an fp16 NHWC tensor
+// (cstride and coff in multiples of 8), dst[0] fp16 (channel stride in multiples of 8).  The plain epilogue only: a residual is refused with everything
+// pnnp_gemm_h1s_launch refuses.  (The caller's validation, pnnp_gemm_x3_check, counts the 2 GB limit of one image in 2-byte elements for such a launch.)
+int pnnp_gemm_h1a_launch(const H2Args& ha, hipStream_t s) {
+    const IgemmArgs& b = ha.g;
+    if (!ha.amax_w || b.amax_out[1] || !b.dst[0]) return PNNP_E_INVALID;
+    if ((((uintptr_t)ha.amax_w) | ((uintptr_t)b.amax_out[0])) & 3) return PNNP_E_INVALID;
+    if (b.mask[0] || b.mask[1] || b.mask_mode[0] || b.mask_mode[1] || b.accum[0] || b.accum[1] || b.dst[1] || ha.bits_out || ha.bits_in[0] || ha.bits_in[1] ||
+        ha.unpool_g || ha.unpool_codes || ha.dgrad_plain || ha.head_out || ha.ksplit > 1 || b.pool_dst || b.pool_codes || b.addsrc) return PNNP_E_UNSUPPORTED;
+    if (b.Ntot % 32 || b.chunks_per_seg <= 0 || (b.dst_cs[0] & 7)) return PNNP_E_UNSUPPORTED;
+    for (int i = 0; i < b.nseg; ++i)
+        if ((b.seg[i].cstride & 7) || (b.seg[i].coff & 7)) return PNNP_E_UNSUPPORTED;
+    H2Args h = ha;
+    h.amax_in[0] = nullptr; h.amax_in[1] = nullptr;
+    if (b.Ntot % 128 == 0) return launch_gs<H1ga, 128, 64, EK_FWD>(h, s);
+    if (b.Ntot % 64 == 0) return launch_gs<H1ga, 64, 32, EK_FWD>(h, s);
+    return launch_gs<H1ga, 32, 32, EK_FWD>(h, s);
+}
 
 // pnnp_gemm_h2s_launch restricted to what an eval forward launches.  `ha.g`: validated like pnnp_gemm_x3_launch's argument (csrc/gemm_x3.hip), with
 // chunks_per_seg = 32-channel items per K segment and Ntot a multiple of 32; weights = the kind-8 pack (csrc/pack_jobs.hip).  Anything with a mask, a bit

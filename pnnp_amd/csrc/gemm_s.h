@@ -35,6 +35,12 @@ constexpr unsigned OOB = 0x80000000u;
 #define GS_VMCNT(N) (0x0f70 | ((N) & 15) | (((N) >> 4) << 14))
 #define GS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")      // (see csrc/conv_s.h: not __syncthreads())
 
+// Element types of the activations (csrc/gemm_h1s.hip H1ga; the 3x3 twin: csrc/conv_s.h SElem): a scheme with SRC16 reads its K segments as fp16 NHWC tensors
+// (one 16-byte load per staging slot, the word goes into the image as loaded: no split, no scale), one with DST16 stores dst[0] as fp16 (one round to
+// nearest even of the float32 value the plain epilogue would store).  A scheme that names neither has float32 on both sides.
+template <class S, class = void> struct GElem { static constexpr bool SRC16 = false, DST16 = false; };
+template <class S> struct GElem<S, std::void_t<decltype(S::SRC16), decltype(S::DST16)>> { static constexpr bool SRC16 = S::SRC16, DST16 = S::DST16; };
+
 template <class Scheme, int BN, int WN_> struct GCfg {
     static constexpr int WN = WN_;                                 // columns per consumer wave: 64 or 32
     static constexpr int OCT = Scheme::CH / 8, OSH = Scheme::CH / 16;      // 8-channel octets of an item: 2 / 4, and their log2
@@ -77,6 +83,10 @@ gemm_s_kernel(const typename Scheme::Args ha) {
     using Cfg = GCfg<Scheme, BN, WN>;
     constexpr int TH = Cfg::TH, PT = Cfg::PT, NB = Cfg::NB, NTW = Cfg::NTW, NSL = Cfg::NSL, D = Cfg::DPW, XS_F4 = Cfg::XS_F4, A = Cfg::A, NSTAGE = Cfg::NSTAGE;
     constexpr int OCT = Cfg::OCT, WBLK1 = Cfg::WBLK1, NP1 = WBLK1 / 1024;      // (NP1: 1 KB LDS-DMA pieces per 32-column block and item)
+    constexpr bool SRC16 = GElem<Scheme>::SRC16, DST16 = GElem<Scheme>::DST16;
+    constexpr int SRC_ES = SRC16 ? 2 : 4, LPS = SRC16 ? 1 : 2;       // bytes per source element; 16-byte loads per staging slot (8 channels)
+    static_assert(!DST16 || EK == EK_FWD, "the epilogue with an fp16 destination");
+    static_assert(!SRC16 || Scheme::PIECES == 1, "an fp16 source is its own single piece");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u32x4* xs = reinterpret_cast<u32x4*>(smem);                     // two activation images
     char* wsb = smem + 2 * Cfg::XS_BYTES;                           // the weight ring
@@ -136,7 +146,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
             xdst[k] = oct * PT + pix;                               // + piece * OCT PT (+ image * XS_F4)
         }
         const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-        f32x4 ra[A][NSL][2];                                        // A register sets: the activations of the next A items
+        f32x4 ra[A][NSL][LPS];                                      // A register sets: the activations of the next A items (SRC16: one word per slot, fp16 as loaded)
         // What a request needs is computed once per (tile, K segment) -- resource, scalar offset, the slots' lane offsets and validity -- and
         // once per tile for the weights; inside a segment the next item is CH channels (4 CH bytes) on, the next k-step of the pack WBLK1 bytes
         // on.  (A producer shares its SIMD with two MFMA waves and gets an issue slot every ~8 cycles: the ~150 instructions of a request
@@ -155,32 +165,37 @@ gemm_s_kernel(const typename Scheme::Args ha) {
                 const IgemmSeg sg = a.seg[q.si];
                 const int mul = a.in_mul;
                 const int shift = (a.IW + 1) * sg.cstride;         // the resource starts before the image: offsets >= -1 pixel stay >= 0
-                la_base = sg.ptr + ((int64_t)tl.b * a.IH * a.IW * sg.cstride - shift);
-                la_soff = (((tl.y0 * mul + sg.yoff) * a.IW + tl.x0 * mul + sg.xoff) * sg.cstride + sg.coff + shift) * 4;
-                const unsigned cs4 = (unsigned)sg.cstride * 4u;
+                const int64_t first = (int64_t)tl.b * a.IH * a.IW * sg.cstride - shift;      // (elements)
+                la_base = SRC16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(sg.ptr) + first) : sg.ptr + first;
+                la_soff = (((tl.y0 * mul + sg.yoff) * a.IW + tl.x0 * mul + sg.xoff) * sg.cstride + sg.coff + shift) * SRC_ES;
+                const unsigned cs4 = (unsigned)sg.cstride * (unsigned)SRC_ES;
 #pragma unroll
                 for (int k = 0; k < NSL; ++k) {
                     const int iy = (tl.y0 + prow[k]) * mul + sg.yoff, ix = (tl.x0 + pcol[k]) * mul + sg.xoff;
                     const int bad = iy | (a.IH - 1 - iy) | ix | (a.IW - 1 - ix) | (a.DH - 1 - tl.y0 - prow[k]) | (a.DW - 1 - tl.x0 - pcol[k]) | (q.ok ? 0 : -1);
-                    la_vo[k] = bad < 0 ? OOB : __umul24((unsigned)((prow[k] * a.IW + pcol[k]) * mul), cs4) + oct * 32;
+                    la_vo[k] = bad < 0 ? OOB : __umul24((unsigned)((prow[k] * a.IW + pcol[k]) * mul), cs4) + oct * (8 * SRC_ES);
                 }
             }
             const __amdgpu_buffer_rsrc_t la_rs = __builtin_amdgcn_make_buffer_rsrc((void*)la_base, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
             for (int k = 0; k < NSL; ++k) {
                 ra[set][k][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(la_rs, la_vo[k], la_soff, 0));
-                ra[set][k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(la_rs, la_vo[k], la_soff + 16, 0));
+                if constexpr (!SRC16) ra[set][k][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(la_rs, la_vo[k], la_soff + 16, 0));
             }
-            la_soff += Scheme::CH * 4;
+            la_soff += Scheme::CH * SRC_ES;
         };
         auto stage_set = [&](auto set_tag, int img) {
             constexpr int set = decltype(set_tag)::value;
 #pragma unroll
             for (int k = 0; k < NSL; ++k) {
+                if constexpr (SRC16) {                               // the eight halves are the image's word: nothing to split, no scale (se_x = 0)
+                    xs[img * XS_F4 + xdst[k]] = __builtin_bit_cast(u32x4, ra[set][k][0]);
+                    continue;
+                }
                 u32x4 sp[Scheme::PIECES];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
-                    const f32x4 v = ra[set][k][p >> 1];
+                    const f32x4 v = ra[set][k][SRC16 ? 0 : p >> 1];
                     unsigned pc[Scheme::PIECES];
                     Scheme::split(v[(p & 1) * 2], v[(p & 1) * 2 + 1], sx, pc);
 #pragma unroll
@@ -232,7 +247,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
             GS_T(t_req)
             stage_set(std::integral_constant<int, (S + 1) % A>{}, (it + 1) & 1);
             GS_T(t_split)
-            __builtin_amdgcn_s_waitcnt(GS_VMCNT(A * 2 * NSL + (A - 1) * D));
+            __builtin_amdgcn_s_waitcnt(GS_VMCNT(A * LPS * NSL + (A - 1) * D));
             GS_T(t_wait)
             step(cu);
             if (!cu.ok) return false;
@@ -365,7 +380,7 @@ gemm_s_kernel(const typename Scheme::Args ha) {
                         const int py = py0 + i, px = px0 + 16 * h;
                         const int oy = py * a.out_mul + yo2, ox = px * a.out_mul + xo2;
                         const bool ok = blk_[k] && py < a.DH && px < a.DW && oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW;
-                        vo[k][i][h] = ok ? (unsigned)(((oy * a.OW + ox) * cs_[k] + chw + c4) * 4) : OOB;
+                        vo[k][i][h] = ok ? (unsigned)(((oy * a.OW + ox) * cs_[k] + chw + c4) * (DST16 ? 2 : 4)) : OOB;      // (bytes of the destination's element type)
                     }
             }
         }
@@ -419,6 +434,37 @@ gemm_s_kernel(const typename Scheme::Args ha) {
             // FULL-LINE memory pattern (csrc/conv_s_body.h): the two 16-column blocks of a 32-column block trade halves between lanes p and p + 8
             // of a 16-lane row, so that each 16-byte store instruction writes 8 pixels x 128 bytes (whole lines) instead of 16 x 64; the
             // act' masks come in by the same pattern and are traded back.
+            if constexpr (DST16) {
+                // 2-byte channels (csrc/conv_s_body.h pack16): the four lanes of a pixel swap quads (v_permlane16_swap) so that 16-lane row q holds the 8 CONSECUTIVE
+                // channels 16 (q & 1) + 8 (q >> 1) .. + 7 of its 32-column block, and one 16-byte store instruction writes 16 pixels x 64 bytes -- through the
+                // ConvTranspose2d scatter (n_sub, out_mul) like the float32 pattern's.  One round to nearest even; amax from the float32 values.
+                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+                const int ch16 = ((lane_e >> 4) & 1) * 16 + (lane_e >> 5) * 8;
+#pragma unroll
+                for (int k = 0; k < NTW; ++k) {
+                    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<_Float16*>(a.dst[0]) + (int64_t)b * a.OH * a.OW * cs_[k]), 0,
+                                                                                        a.OH * a.OW * cs_[k] * 2, 0x00020000);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const f32x4 v0 = raw(2 * i + h, 2 * k), v1 = raw(2 * i + h, 2 * k + 1);
+                            f32x4 o0, o1;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) { o0[c] = __builtin_fmaf(v0[c], dsc, bias4[2 * k][c]); o1[c] = __builtin_fmaf(v1[c], dsc, bias4[2 * k + 1][c]); }
+                            o0 = act4(o0); o1 = act4(o1);           // (no branch: without an activation the slope is 1 and max(o, 1 o) = o bit for bit)
+                            track(o0, vo[k][i][h] != OOB, du_[k]); track(o1, vo[k][i][h] != OOB, du_[k]);
+                            const unsigned a0 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o0.x, (_Float16)o0.y}), a1 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o0.z, (_Float16)o0.w});
+                            const unsigned b0 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o1.x, (_Float16)o1.y}), b1 = __builtin_bit_cast(unsigned, f16x2{(_Float16)o1.z, (_Float16)o1.w});
+                            const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false), s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+                            // vo: the byte offset of (pixel, channel chw + c4) in 2-byte elements; the word of this lane starts at channel chw + ch16
+                            const unsigned off = vo[k][i][h] != OOB ? vo[k][i][h] + (unsigned)((ch16 - c4) * 2) : OOB;
+                            __builtin_amdgcn_raw_buffer_store_b128(u32x4{s0[0], s1[0], s0[1], s1[1]}, rd, off, 0, GEMMS_STORE_AUX);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                }
+                return;
+            }
             const bool lo8 = p16 < 8;
             auto ror8 = [&](f32x4 v) {
                 float r0, r1, r2, r3;

@@ -4,25 +4,29 @@
 #include "igemm.h"
 
 int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s);
-int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg);        // the validation alone (csrc/conv_api.hip: the fp16x2 entries share it)
+int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg, int src_es = 4, int dst_es = 4);        // the validation alone (csrc/conv_api.hip: the fp16 entries share it)
 int pnnp_gemm_x3s_launch(const IgemmArgs& a, hipStream_t s);        // csrc/gemm_x3s.hip
 
 namespace { constexpr int WBLK = 2 * 3 * 32 * 16; }                 // one 16-channel k-step of one 32-column block: [octet 2][piece 3][32][16 B] = 3072
 
 // a.w: x3 pack with ONE tap: [N/32][K/16][octet 2][piece 3][32][8 bf16].  chan_per_seg: channels per K segment, a multiple of 32.
-int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg) {
+// src_es / dst_es: bytes per element of the K segments / of dst[0] (2: fp16 maps of csrc/gemm_h1s.hip H1ga -- 16-byte words are then 8 channels, and the
+// 2 GB limit of one image is counted in 2-byte elements)
+int pnnp_gemm_x3_check(const IgemmArgs& a, int chan_per_seg, int src_es, int dst_es) {
+    const int src_q = 16 / src_es - 1, dst_q = 16 / dst_es - 1;
+    if (dst_es != 4 && a.dst[1]) return PNNP_E_UNSUPPORTED;
     if (a.nseg < 1 || a.nseg > 9 || chan_per_seg <= 0 || (chan_per_seg & 31) || a.Ntot <= 0) return PNNP_E_INVALID;
     if ((a.Ntot & 31) || a.in_mul < 1 || a.in_mul > 2 || (a.n_sub & 31) || (a.dst[1] && (a.n_split & 31))) return PNNP_E_UNSUPPORTED;
     if (a.addsrc && a.accum[0]) return PNNP_E_UNSUPPORTED;
-    if ((a.dst_cs[0] & 3) || (a.dst[1] && (a.dst_cs[1] & 3))) return PNNP_E_UNSUPPORTED;
+    if ((a.dst_cs[0] & dst_q) || (a.dst[1] && (a.dst_cs[1] & 3))) return PNNP_E_UNSUPPORTED;
     if ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.bias) | ((uintptr_t)a.mask[0]) | ((uintptr_t)a.mask[1]) |
          ((uintptr_t)a.addsrc) | ((uintptr_t)a.w)) & 15) return PNNP_E_INVALID;
     for (int i = 0; i < a.nseg; ++i) {
-        if (a.seg[i].yoff < -1 || a.seg[i].xoff < -1 || (a.seg[i].cstride & 3) || (((uintptr_t)a.seg[i].ptr) & 15)) return PNNP_E_UNSUPPORTED;
-        if (((int64_t)a.IH + 4) * a.IW * a.seg[i].cstride * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+        if (a.seg[i].yoff < -1 || a.seg[i].xoff < -1 || (a.seg[i].cstride & src_q) || (src_es != 4 && (a.seg[i].coff & src_q)) || (((uintptr_t)a.seg[i].ptr) & 15)) return PNNP_E_UNSUPPORTED;
+        if (((int64_t)a.IH + 4) * a.IW * a.seg[i].cstride * src_es >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     }
     for (int d = 0; d < 2; ++d)
-        if (a.dst[d] && (int64_t)a.OH * a.OW * a.dst_cs[d] * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+        if (a.dst[d] && (int64_t)a.OH * a.OW * a.dst_cs[d] * (d ? 4 : dst_es) >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     return PNNP_OK;
 }
 int pnnp_gemm_x3_launch(const IgemmArgs& a, int chan_per_seg, hipStream_t s) {

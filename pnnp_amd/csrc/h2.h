@@ -56,6 +56,8 @@ struct H2Args {
 // so a lane reads back exactly the word the same lane position wrote: 4 bytes per lane instead of 8 x 16.
 int pnnp_igemm_h2s_launch(const H2Args& a, int chan_per_seg, hipStream_t s);
 int pnnp_igemm_h1s_launch(const H2Args& a, int chan_per_seg, hipStream_t s);      // csrc/conv_h1s.hip (fp16x1: eval forward only)
+int pnnp_igemm_h1a_launch(const H2Args& a, int chan_per_seg, int src_f16, int dst_f16, hipStream_t s);      // ... with fp16 activations on either side (csrc/conv_h1s.hip H1a)
+int pnnp_h1_splitk_reduce_f16_launch(const float* slab, int S, const float* bias, void* y, unsigned* amax, int B, int H, int W, int N, int act, hipStream_t st);
 int pnnp_h2_splitk_reduce_launch(const float* slab, int S, const float* bias, float* y, unsigned* bits, unsigned* amax, int B, int H, int W, int N, int act, hipStream_t st);
 
 // hi = f16(a s), lo = f16(a s - hi) of two values, packed (low half = a0): v_fma_mix*_f16 computes the fma in float32 and rounds ONCE to fp16

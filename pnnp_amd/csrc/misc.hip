@@ -60,6 +60,28 @@ nhwc_to_nchw_kernel(const float* __restrict__ src, const float* __restrict__ res
 }
 
 // NHWC 2x2 max pool, one thread per 4 channels of one output pixel.
+// MaxPool2d(2) of an fp16 NHWC map (a pooled layer of an fp16-storage forward that ran split-K: no pool in its epilogue): 8 channels = 16 bytes per thread; the
+// maximum of four fp16 values is one of them (NaN: v_pk_max_f16 returns the other operand, as the float32 pass's fmaxf does)
+__global__ void __launch_bounds__(256)
+h1_maxpool2_f16_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t total, int OH, int OW, int C8) {
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int c = (int)(e % C8); int64_t p = e / C8;
+        const int ox = (int)(p % OW); p /= OW;
+        const int oy = (int)(p % OH); const int64_t b = p / OH;
+        const u32x4* r0 = x + ((b * 2 * OH + 2 * oy) * 2 * OW + 2 * ox) * C8 + c;
+        const u32x4* r1 = r0 + (int64_t)2 * OW * C8;
+        const u32x4 v00 = r0[0], v01 = r0[C8], v10 = r1[0], v11 = r1[C8];
+        // (word by word, written out: as a loop over o[k] the compiler kept the first word only)
+        auto mx = [](unsigned p00, unsigned p01, unsigned p10, unsigned p11) {
+            const f16x2 m0 = __builtin_elementwise_max(__builtin_bit_cast(f16x2, p00), __builtin_bit_cast(f16x2, p01));
+            const f16x2 m1 = __builtin_elementwise_max(__builtin_bit_cast(f16x2, p10), __builtin_bit_cast(f16x2, p11));
+            return __builtin_bit_cast(unsigned, __builtin_elementwise_max(m0, m1));
+        };
+        y[e] = u32x4{mx(v00.x, v01.x, v10.x, v11.x), mx(v00.y, v01.y, v10.y, v11.y), mx(v00.z, v01.z, v10.z, v11.z), mx(v00.w, v01.w, v10.w, v11.w)};
+    }
+}
+
 __global__ void __launch_bounds__(256)
 maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C) {
     const int h = H / 2, w = W / 2, cq = C / 4;
@@ -370,6 +392,17 @@ int pnnp_maxpool2_fwd_f32(const float* x, float* y, int B, int H, int W, int C, 
     if (!x || !y || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || (C & 3)) return PNNP_E_INVALID;
     if (B == 0) return PNNP_OK;
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid1d((int64_t)B * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0, as_stream(stream), x, y, B, H, W, C);
+    return pnnp_launch_status();
+}
+
+// y [B][H/2][W/2][C] = MaxPool2d(2)(x [B][H][W][C]), both fp16 NHWC; H, W even, C a multiple of 8, 16-byte aligned
+int pnnp_maxpool2_fwd_f16(const void* x, void* y, int B, int H, int W, int C, void* stream) {
+    if (!x || !y || B < 0 || H <= 0 || W <= 0 || C <= 0 || (H & 1) || (W & 1) || (C & 7) || ((((uintptr_t)x) | ((uintptr_t)y)) & 15)) return PNNP_E_INVALID;
+    const int64_t total = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
+    if (total <= 0) return PNNP_OK;
+    const int64_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(h1_maxpool2_f16_kernel, dim3((unsigned)(blocks > 65535 ? 65535 : blocks)), dim3(256), 0, as_stream(stream), static_cast<const u32x4*>(x),
+                       static_cast<u32x4*>(y), total, H / 2, W / 2, C / 8);
     return pnnp_launch_status();
 }
 

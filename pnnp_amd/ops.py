@@ -536,6 +536,90 @@ conv_h2_fwd_head, conv_h1_fwd_head = _for_family(conv_f16_fwd_head, 'h2'), _for_
 conv_h2_fwd_pool, conv_h1_fwd_pool = _for_family(conv_f16_fwd_pool, 'h2'), _for_family(conv_f16_fwd_pool, 'h1')
 
 
+# ---- the fp16x1 layers with fp16 ACTIVATIONS ("h1a": csrc/conv_h1s.hip H1a, the pnnp_conv3x3_h1_*_et entries).  The element type of a side is the dtype of its
+# tensors: torch.float16 NHWC sources are taken as they are (unscaled; no amax slot), a torch.float16 ``y`` / ``pooled`` receives float16(the float32 value the
+# conv_h1_* wrapper stores).  float32 on both sides is that wrapper.  Anything else -- another dtype, x2 unlike x1, pooled unlike y -- is refused HERE.
+def image_fits(H, W, cstride, elem_bytes=4):
+    """one [H][W][cstride] image of ``elem_bytes``-byte elements within the 32-bit byte offsets of the matrix-core kernels?  (4: x3_image_fits)"""
+    return bool(_prep().pnnp_image_fits_es(int(H), int(W), int(cstride), int(elem_bytes)))
+
+
+def _h1a_types(what, x1, x2, y, *same_as_y):
+    """(src_f16, dst_f16) of a launch from its tensors' dtypes; ``y`` None: a float32 destination"""
+    def is16(t, role):
+        if t.dtype not in (torch.float16, torch.float32):
+            raise _lib.PnnpError(f'{what}: {role} is {t.dtype}: torch.float16 or torch.float32')
+        return t.dtype == torch.float16
+    s16 = is16(x1, 'x1')
+    if x2 is not None and is16(x2, 'x2') != s16:
+        raise _lib.PnnpError(f'{what}: x1 is {x1.dtype} and x2 {x2.dtype}: the K segments of a launch share one element type')
+    d16 = is16(y, 'y') if y is not None else False
+    for t in same_as_y:
+        if t is not None and t.dtype != y.dtype:
+            raise _lib.PnnpError(f'{what}: {t.dtype} beside a {y.dtype} destination')
+    return int(s16), int(d16)
+
+
+def _h1a_bytes(B, H, W, C1, C2, cout, s16, d16):
+    return B * H * W * ((C1 + C2) * (2.0 if s16 else 4.0) + cout * (2.0 if d16 else 4.0))
+
+
+def conv_h1a_fwd(x1, x2, w, amax_w, bias, y, cout, act, amax_x1=None, amax_x2=None, amax_y=None):
+    """conv_h1_fwd with the element types of ``x1`` / ``x2`` and ``y`` (no residual)"""
+    s16, d16 = _h1a_types('conv_h1a_fwd', x1, x2, y)
+    require_cuda(x1, x2, w, y, amax_w)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9, _h1a_bytes(B, H, W, C1, C2, cout, s16, d16), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
+        check(_prep().pnnp_conv3x3_h1_fwd_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16,
+                                             B, H, W, cout, act, stream()), 'conv_h1a_fwd')
+    return y
+
+
+def conv_h1a_fwd_splitk(x1, x2, w, amax_w, bias, y, cout, act, ksplit, ws, amax_x1=None, amax_x2=None, amax_y=None):
+    """conv_h1_fwd_splitk with element types: the slabs ``ws`` stay float32, the reduce rounds once into an fp16 ``y``"""
+    s16, d16 = _h1a_types('conv_h1a_fwd_splitk', x1, x2, y)
+    if ws.dtype != torch.float32:
+        raise _lib.PnnpError(f'conv_h1a_fwd_splitk: the slabs are float32, ws is {ws.dtype}')
+    require_cuda(x1, x2, w, y, amax_w, ws)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9, _h1a_bytes(B, H, W, C1, C2, cout, s16, d16), sub='splitk'):
+        check(_prep().pnnp_conv3x3_h1_fwd_splitk_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16,
+                                                    B, H, W, cout, act, int(ksplit), ptr(ws), _i64(ws.numel()), stream()), 'conv_h1a_fwd_splitk')
+    return y
+
+
+def conv_h1a_fwd_head(x1, x2, w, amax_w, bias, cout, act, head_w, head_b, out, amax_x1=None, amax_x2=None, residual=None):
+    """conv_h1_fwd_head of an fp16 source: ``out`` float32 NCHW [B,4,H,W] (+ ``residual``), nothing else stored"""
+    s16, _ = _h1a_types('conv_h1a_fwd_head', x1, x2, None)
+    for t in (head_w, head_b, out, residual):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.PnnpError(f'conv_h1a_fwd_head: the head is float32, got {t.dtype}')
+    require_cuda(x1, x2, w, amax_w, head_w, out, residual)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9 + 2.0 * B * H * W * cout * 4, _h1a_bytes(B, H, W, C1, C2, 0, s16, 0) + 16.0 * B * H * W, sub='bn32'):
+        check(_prep().pnnp_conv3x3_h1_fwd_head_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(head_w), ptr(head_b),
+                                                  ptr(residual), ptr(out), s16, B, H, W, cout, act, stream()), 'conv_h1a_fwd_head')
+    return out
+
+
+def conv_h1a_fwd_pool(x1, x2, w, amax_w, bias, y, pooled, codes, cout, act, amax_x1=None, amax_x2=None, amax_y=None):
+    """conv_h1_fwd_pool with element types: ``pooled`` has the dtype of ``y``; the ``codes`` are those of the float32 map"""
+    s16, d16 = _h1a_types('conv_h1a_fwd_pool', x1, x2, y, pooled)
+    if codes.dtype != torch.uint8:
+        raise _lib.PnnpError(f'conv_h1a_fwd_pool: the codes are bytes, got {codes.dtype}')
+    require_cuda(x1, x2, w, y, pooled, codes, amax_w)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9, _h1a_bytes(B, H, W, C1, C2, 1.25 * cout, s16, d16) + B * H * W * cout / 4,
+                sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout, True)):
+        check(_prep().pnnp_conv3x3_h1_fwd_pool_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(pooled), ptr(codes),
+                                                  ptr(amax_y), s16, d16, B, H, W, cout, act, stream()), 'conv_h1a_fwd_pool')
+    return y
+
+
 def conv_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx1, mask1=None, bits1=None, mode1=0, accum1=0, amax_dx1=None,
                      dx2=None, mask2=None, bits2=None, mode2=0, accum2=0, amax_dx2=None):
     require_cuda(g, w_h2_dgrad, dx1, amax_g, amax_w)
@@ -635,8 +719,20 @@ def conv_s2_f16_fwd(fam, x, amax_x, w, amax_w, bias, y, cout, act, amax_y=None):
 
 
 convt_h2_fwd, convt_h1_fwd = _for_family(convt_f16_fwd, 'h2'), _for_family(convt_f16_fwd, 'h1')
+
 conv1x1_h2_fwd, conv1x1_h1_fwd = _for_family(conv1x1_f16_fwd, 'h2'), _for_family(conv1x1_f16_fwd, 'h1')
 conv_s2_h2_fwd, conv_s2_h1_fwd = _for_family(conv_s2_f16_fwd, 'h2'), _for_family(conv_s2_f16_fwd, 'h1')
+
+
+def convt_h1a_fwd(x, w, amax_w, bias, y, cout, amax_x=None, amax_y=None):
+    """convt_h1_fwd with the element types of ``x`` and ``y`` (csrc/gemm_h1s.hip H1ga): both torch.float16 -- x taken as it is, y = float16(the float32 value
+    convt_h1_fwd stores) -- or both float32 (that wrapper); a mixed pair is refused by the entry"""
+    s16, d16 = _h1a_types('convt_h1a_fwd', x, None, y)
+    require_cuda(x, w, y, amax_w)
+    B, H, W, Cin = x.shape
+    with _Timed('convt_fwd_h1a', 8.0 * B * H * W * Cin * cout, B * H * W * ((2.0 if s16 else 4.0) * Cin + (2.0 if d16 else 4.0) * 4 * cout)):
+        check(_prep().pnnp_convt_h1_fwd_et(ptr(x), Cin, ptr(amax_x), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16, B, H, W, cout, stream()), 'convt_h1a_fwd')
+    return y
 
 
 def convt_h2_bwd_data(g, amax_g, w_h2_dgrad, amax_w, dx, mask=None, mode=0, amax_dx=None, bits=None):
@@ -1037,6 +1133,17 @@ def maxpool_fwd(x, y, codes=None):
         check(_prep().pnnp_maxpool2_fwd_codes_f32(ptr(x), ptr(y), ptr(codes), B, H, W, Cc, stream()), 'maxpool_fwd_codes')
     else:
         check(_prep().pnnp_maxpool2_fwd_f32(ptr(x), ptr(y), B, H, W, Cc, stream()), 'maxpool_fwd')
+    return y
+
+
+def maxpool_fwd_f16(x, y):
+    """MaxPool2d(2) of a torch.float16 NHWC map into a torch.float16 one (the fp16-storage eval forward; no codes: nothing runs backward)"""
+    if x.dtype != torch.float16 or y.dtype != torch.float16:
+        raise _lib.PnnpError(f'maxpool_fwd_f16: torch.float16 maps, got {x.dtype} -> {y.dtype}')
+    require_cuda(x, y)
+    B, H, W, Cc = x.shape
+    with _Timed('maxpool_fwd_f16', 0.0, 2.5 * B * H * W * Cc):
+        check(_prep().pnnp_maxpool2_fwd_f16(ptr(x), ptr(y), B, H, W, Cc, stream()), 'maxpool_fwd_f16')
     return y
 
 

@@ -101,13 +101,76 @@ def per_layer(net, x, names, reps=5, kinds=CONV3):
     return {n: float(np.median(v[1:])) for n, v in acc.items()}
 
 
+def act16_main(a):
+    """'fp16_act' (ConvPolicy.h1_act16: every map a convolution writes and a convolution reads stored as fp16) alternated with 'fp32' / 'fp16' / 'fp16_all' in
+    one process; the yardstick of the new column is the 'fp16_all' column of the SAME run.  UNet only: ResUnet's plan is its fp16_all plan."""
+    out = a.out
+    g = torch.Generator(device='cuda').manual_seed(1)
+    u2, u1, ua, sd = make('unet')
+    uc = UNetSeeInDark(dict(nframes=1, res=False, nf=32, in_nc=4, out_nc=4))
+    uc.load_state_dict({k: v.clone() for k, v in sd.items()})
+    uc = uc.cuda().eval()
+    uc.engine.set_policy(h1_eval=True, h1_pointwise=True, h1_act16=True)
+    hr = sid_like((1, 4, H, W), g)
+    frame = (hr + 0.02 * torch.randn(1, 4, H, W, device='cuda', generator=g)).clamp(0, 1)
+    crop1 = frame[:, :, 400:912, 800:1312].contiguous()
+    crops16 = torch.cat([frame[:, :, 64 * i:64 * i + 512, 100 * i:100 * i + 512] for i in range(14)] + [crop1, crop1.flip(-1)]).contiguous()
+    L = [f"fp16 storage of the activations ('fp16_act') against 'fp16_all', 'fp16' and 'fp32' on {torch.cuda.get_device_name(0)}; UNet nf = 32; random variance-preserving weights",
+         f'per call, median [min .. max] over {a.reps} rounds, the four modes alternated inside every round (four engines, same weights: no re-pack is timed); device events', '']
+
+    def fwd(net, x):
+        def f():
+            with torch.no_grad():
+                net.engine.forward(x, False)
+        return f
+    nets = {'fp32': u2, 'fp16': u1, 'fp16_all': ua, 'fp16_act': uc}
+    work = [('1 crop 4x512x512', lambda n: fwd(n, crop1), 20), ('16 crops 4x512x512', lambda n: fwd(n, crops16), 4), (f'whole frame 4x{H}x{W}', lambda n: fwd(n, frame), 4),
+            ('forward_tiled, 20 tiles of 512', lambda n: (lambda: forward_tiled(n, frame, P, BASE)), 3)]
+    L.append('(a) eval forward')
+    for name, mk, inner in work:
+        res = rounds({k: mk(n) for k, n in nets.items()}, a.reps, inner)
+        ma, mc = np.median(res['fp16_all']), np.median(res['fp16_act'])
+        L.append(f'  {name}')
+        for k in nets:
+            L.append(f'    {k:9s}{stat(res[k])}')
+        L.append(f'    fp16_all / fp16_act = {ma / mc:.3f} x  (spread of the fp16_all rounds: {100 * (max(res["fp16_all"]) - min(res["fp16_all"])) / ma:.1f} % of their median)')
+    assert uc.engine._plan.act16 and not ua.engine._plan.act16
+    L.append('')
+    order = [f'conv{i}_{j}' for i in range(1, 6) for j in (1, 2)]
+    for i in range(6, 10):
+        order += [f'upv{i}', f'conv{i}_1', f'conv{i}_2']
+    show = ('conv1_1', 'conv1_2', 'upv9', 'conv9_1', 'conv9_2', 'conv5_1', 'conv5_2', 'upv6', 'conv6_1')
+    for label, x in (('16 crops 4x512x512', crops16), (f'whole frame 4x{H}x{W}', frame)):
+        ta = per_layer(ua, x, order, kinds=('conv9_fwd_h1', 'convt_fwd_h1'))
+        tc = per_layer(uc, x, order, kinds=('conv9_fwd_h1a', 'convt_fwd_h1a'))
+        L.append(f'(b) {label}: launches one by one (events around every launch: sums exceed (a)); conv9_2 carries the head')
+        for n in show:
+            L.append(f'    {n:8s} {uc.engine._plan[n].fwd:10s} fp16_all {ta[n]:8.1f} us   fp16_act {tc[n]:8.1f} us   fp16_all / fp16_act = {ta[n] / tc[n]:.3f} x')
+        L.append(f'    all 22 launches: fp16_all {sum(ta.values()):.1f} us, fp16_act {sum(tc.values()):.1f} us')
+    L.append('')
+    with torch.no_grad():
+        ya, yc = ua(crop1), uc(crop1)
+    L.append(f'(c) 512 x 512 crop, fp16_act against fp16_all: PSNR {psnr(yc, ya):.1f} dB, max |difference| {float((yc - ya).abs().max()):.2e} of outputs up to {float(ya.abs().max()):.2f}')
+    rng = uc.engine.act16_range()
+    L.append(f'    act16_range: largest map amax {max(r["amax"] for r in rng):.3g} ({max(rng, key=lambda r: r["amax"])["name"]}), overflow flags {sum(r["overflow"] for r in rng)}')
+    text = '\n'.join(L) + '\n'
+    print(text)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'r7', 'h1_pointwise.txt'))
+    ap.add_argument('--out', default=None, help='default: profiles/r7/h1_pointwise.txt, or profiles/r7/act16.txt with --act16')
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--act16', action='store_true', help="the 'fp16_act' column (fp16 storage of the activations, UNet) beside the three others -> profiles/r7/act16.txt")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('h1_eval_bench needs the GPU: nothing here is measured without one')
+    a.out = a.out or os.path.join(REPO, 'profiles', 'r7', 'act16.txt' if a.act16 else 'h1_pointwise.txt')
+    if a.act16:
+        return act16_main(a)
     g = torch.Generator(device='cuda').manual_seed(1)
     u2, u1, ua, sd_u = make('unet')
     r2, r1, ra, _ = make('resunet')

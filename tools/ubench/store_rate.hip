@@ -5,6 +5,8 @@
 //   kind 2: buffer_store_dword in the 16x16 MFMA accumulator layout: lanes 0-15 = 64 contiguous bytes of one pixel, lane groups 4 pixels
 //           apart ... i.e. 4 x 64-byte segments, pixel stride `cs` floats (what a store straight from the accumulators would do)
 //   kind 3: buffer_store_dword in the 32x32 accumulator layout: lanes 0-31 = 128 contiguous bytes of one pixel, lanes 32-63 of the pixel 4 further
+//   kind 6 / 7 (fp16 maps, csrc/conv_s_body.h pack16): buffer_store_dwordx4 of 16 pixels x 64 B / of 8 pixels x 128 B per instruction at a pixel stride of `cs`
+//           BYTES (64: a 32-channel fp16 map, 16 px x 64 B is then 1 KB contiguous; 128 / 256 / 512: 64 / 128 / 256 channels)
 // usage: store_rate [workgroups = 256] [stores per wave = 256]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -22,6 +24,8 @@ __global__ void __launch_bounds__(512, 1) store_kernel(float* dst, long long wg_
     else if (KIND == 2) { vo = ((wave * 64 + 4 * (lane >> 4)) * cs + (lane & 15)) * 4; step = 4; }      // r = 0..3 -> + cs floats; 16 columns on: + 64 B
     else if (KIND == 3) { vo = ((wave * 64 + 4 * (lane >> 5)) * cs + (lane & 31)) * 4; step = 4; }
     else if (KIND == 4) { vo = ((wave * 64 + (lane & 15)) * cs + (lane >> 4) * 4) * 4; step = 64; }       // b128: 16 pixels x 64 B per instruction (conv_x3s epilogue)
+    else if (KIND == 6) { vo = (wave * 64 + (lane & 15)) * cs + (lane >> 4) * 16; step = 0; }
+    else if (KIND == 7) { vo = (wave * 64 + (lane >> 3)) * cs + (lane & 7) * 16; step = 0; }
     else { vo = ((wave * 64 + (lane >> 3)) * cs + (lane & 7) * 4) * 4; step = 128; }                    // b128: 8 pixels x 128 B per instruction (round 3's LDS-patch epilogue)
     const u32x4 v = {(unsigned)tid, 1u, 2u, 3u};
     __syncthreads();
@@ -40,6 +44,12 @@ __global__ void __launch_bounds__(512, 1) store_kernel(float* dst, long long wg_
         } else if (KIND == 5) {
             const int j = i & 1, h = (i >> 1) & 7, rest = i >> 4;          // 2 x 32-channel blocks, then 8 pixels on
             __builtin_amdgcn_raw_buffer_store_b128(v, rd, vo, ((8 * h + 512 * rest) * cs + 32 * j) * 4, 0);
+        } else if (KIND == 6) {
+            const int nb = cs / 64, j = i % nb, h = (i / nb) & 3, rest = i / (4 * nb);      // the 64-byte blocks of a pixel, then 16 pixels on
+            __builtin_amdgcn_raw_buffer_store_b128(v, rd, vo, (16 * h + 512 * rest) * cs + 64 * j, 0);
+        } else if (KIND == 7) {
+            const int nb = cs / 128, j = i % nb, h = (i / nb) & 7, rest = i / (8 * nb);     // the 128-byte lines of a pixel, then 8 pixels on
+            __builtin_amdgcn_raw_buffer_store_b128(v, rd, vo, (8 * h + 512 * rest) * cs + 128 * j, 0);
         } else {
             const int r = i & 3, g = (i >> 2) & 3, j = (i >> 4) & 1, rest = i >> 5;       // rows r + 8 g (+ 4 by the lane half), 32-channel block j
             __builtin_amdgcn_raw_buffer_store_b32(v[0], rd, vo, ((r + 8 * g + 512 * rest) * cs + 32 * j) * 4, 0);
@@ -51,13 +61,13 @@ __global__ void __launch_bounds__(512, 1) store_kernel(float* dst, long long wg_
     if (lane == 0) { out[(blockIdx.x * 8 + wave) * 2] = t1 - t0; out[(blockIdx.x * 8 + wave) * 2 + 1] = t2 - t0; }
     if (lds[tid] == 0x7fffffff) out[0] = 0;
 }
-template <int KIND> void run(int wgs, int n, float* dst, long long stride, long long* out, const char* name, double bytes_per_store) {
+template <int KIND> void run(int wgs, int n, float* dst, long long stride, long long* out, const char* name, double bytes_per_store, int cs = 64) {
     hipFuncSetAttribute((const void*)store_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     float ms = 0;
     for (int rep = 0; rep < 3; ++rep) {
         hipEventRecord(e0);
-        hipLaunchKernelGGL(store_kernel<KIND>, dim3(wgs), dim3(512), 160 * 1024, 0, dst, stride, n, 64, out);
+        hipLaunchKernelGGL(store_kernel<KIND>, dim3(wgs), dim3(512), 160 * 1024, 0, dst, stride, n, cs, out);
         hipEventRecord(e1); hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1);
     }
     long long* h = (long long*)malloc(wgs * 16 * 8); hipMemcpy(h, out, wgs * 16 * 8, hipMemcpyDeviceToHost);
@@ -79,5 +89,12 @@ int main(int argc, char** argv) {
     run<0>(wgs, n / 4, dst, stride, out, "dwordx4, same bytes as the dwords", 1024);
     run<4>(wgs, n, dst, stride, out, "dwordx4, 16 px x 64 B (cs = 64)", 1024);
     run<5>(wgs, n, dst, stride, out, "dwordx4, 8 px x 128 B (cs = 64)", 1024);
+    run<6>(wgs, n, dst, stride, out, "fp16 16 px x 64 B, stride 64 B", 1024, 64);
+    run<6>(wgs, n, dst, stride, out, "fp16 16 px x 64 B, stride 128 B", 1024, 128);
+    run<7>(wgs, n, dst, stride, out, "fp16 8 px x 128 B, stride 128 B", 1024, 128);
+    run<6>(wgs, n, dst, stride, out, "fp16 16 px x 64 B, stride 256 B", 1024, 256);
+    run<7>(wgs, n, dst, stride, out, "fp16 8 px x 128 B, stride 256 B", 1024, 256);
+    run<6>(wgs, n, dst, stride, out, "fp16 16 px x 64 B, stride 512 B", 1024, 512);
+    run<7>(wgs, n, dst, stride, out, "fp16 8 px x 128 B, stride 512 B", 1024, 512);
     return 0;
 }
