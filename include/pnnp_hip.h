@@ -312,6 +312,21 @@ int pnnp_conv3x3_h1_fwd_pool_et(const void* x1, int C1, const unsigned* amax_x1,
  * PNNP_E_UNSUPPORTED.  One image of x / y must stay below 2 GB in 2-byte elements. */
 int pnnp_convt_h1_fwd_et(const void* x, int Cin, const unsigned* amax_x /*or null for fp16*/, const void* w_h1, const unsigned* amax_w, const float* bias /*or null*/,
                          void* y, unsigned* amax_y /*or null*/, int src_f16, int dst_f16, int B, int H, int W, int Cout, void* stream);
+/* ---- ... and the layers only ResUnet has, with fp16 on EVERY side (ConvPolicy.h1_act16_res; the same storage contract):
+ *   pnnp_conv3x3_h1_fwd_res_et: pnnp_conv3x3_h1_fwd_f32 with a residual: y16 = float16((acc 2^dexp + bias) + float(r16)), the sum made in float32 in that order
+ *     and rounded ONCE; amax_y records the float32 sum.  residual: an fp16 NHWC tensor with y's geometry.  Offered for src_f16 = res_f16 = dst_f16 = 1 (and
+ *     all three 0: the _f32 twin); any other triple, or act != 0: PNNP_E_UNSUPPORTED.  A null residual: PNNP_E_INVALID.
+ *   pnnp_conv_s2_h1_fwd_et / pnnp_conv1x1_h1_fwd_et: the stride-2 3x3 layer and the 1x1 layer on cat([x1, x2]) (kind-8 packs) with x and y both fp16 (1, 1) or
+ *     the twin (0, 0); a mixed pair is PNNP_E_UNSUPPORTED.  An fp16 source has no amax slot (null allowed).  The fp16 1x1 layer takes no residual (PNNP_E_UNSUPPORTED).  Channel
+ *     strides in multiples of 8; one image of a map below 2 GB in 2-byte elements. */
+int pnnp_conv3x3_h1_fwd_res_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                               const unsigned* amax_w, const float* bias /*or null*/, const void* residual, void* y, unsigned* amax_y /*or null*/,
+                               int src_f16, int res_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv_s2_h1_fwd_et(const void* x, int Cin, const unsigned* amax_x /*or null for fp16*/, const void* w_h1, const unsigned* amax_w, const float* bias /*or null*/,
+                           void* y, unsigned* amax_y /*or null*/, int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream);
+int pnnp_conv1x1_h1_fwd_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2 /*or null*/, int C2, const unsigned* amax_x2, const void* w_h1,
+                           const unsigned* amax_w, const float* bias /*or null*/, const float* residual /*null with fp16*/, void* y, unsigned* amax_y /*or null*/,
+                           int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream);
 int pnnp_conv3x3_h2_bwd_data_f32(const float* g, int Cout, const unsigned* amax_g, const void* w_h2_dgrad, const unsigned* amax_w,
                                  float* dx1, int C1, const float* mask1, const unsigned* bits1, int mode1, int accum1, unsigned* amax_dx1,
                                  float* dx2 /*or null*/, int C2, const float* mask2, const unsigned* bits2, int mode2, int accum2, unsigned* amax_dx2,
@@ -544,6 +559,16 @@ int pnnp_first_fwd_amax_f32(const float* x, int xcs, int cin, const float* w, co
                             int B, int H, int W, int cout, int act, unsigned* amax_y /*or null: max |y| into an amax slot*/, void* stream);
 int pnnp_first_bwd_weight_f32(const float* g, int gcs, int cout, const float* x, int xcs, int cin, float* dW, float* dbias /*or null*/,
                               int B, int H, int W, int accumulate, float* ws, int64_t ws_floats, void* stream);
+/* ... with an element type on the side that faces the network (the fp16-storage eval forward of ResUnet, ConvPolicy.h1_act16_res):
+ *   first forward, dst_f16 != 0: y is an fp16 NHWC tensor = float16(v) of the float32 value v the _f32 twin stores -- one round to nearest even, unscaled,
+ *     not saturated; amax_y still max |v|.  x stays float32.
+ *   head forward, src_f16 != 0: x is an fp16 NHWC tensor (8-byte aligned, xcs in multiples of 4), widened exactly; fed x16 where the twin is fed float(x16)
+ *     the outputs agree bit for bit.  w, bias, residual, out stay float32.
+ * dst_f16 / src_f16 = 0: the twin itself. */
+int pnnp_first_fwd_amax_et(const float* x, int xcs, int cin, const float* w, const float* bias /*or null*/, void* y, int ycs,
+                           int B, int H, int W, int cout, int act, unsigned* amax_y /*or null*/, int dst_f16, void* stream);
+int pnnp_head_fwd_et(const void* x, int xcs, int cin, const float* w /*[cout][cin]*/, const float* bias, const float* residual /*or null*/,
+                     float* out, int src_f16, int B, int H, int W, int cout, void* stream);
 /* boundary layout changes: NCHW [B][C][H][W] <-> NHWC [B][H][W][Cp] (Cp >= C, zero padded);
  * the NCHW result can add a residual (arch 'res' flag, archs/Unet.py:95-98). */
 int pnnp_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int H, int W, int Cp, void* stream);

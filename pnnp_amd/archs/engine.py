@@ -60,7 +60,7 @@ class _EngineBase:
         if policy is None:
             cur = dict(wino=self.policy.wino, wino_wgrad=self.policy.wino_wgrad, wino_mink=self.policy.wino_mink, x3=self.policy.x3,
                        thin=self.policy.thin, pool_fused=self.policy.pool_fused, h2=self.policy.h2)
-            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval', 'h1_pointwise', 'h1_act16'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
+            for k in ('h2_wgrad', 'h2_pointwise', 'head_fused', 'splitk', 'convt_bits', 'unpool_fused', 'h1_eval', 'h1_pointwise', 'h1_act16', 'h1_act16_res'):   # sub-switches of h2 (host-side A/B): not constructor arguments, kept as overrides
                 if k in kw:
                     self._h2_sub[k] = bool(kw.pop(k))
             if 'unpool_levels' in kw:                              # which encoder levels unpool_fused applies to (plan.py)
@@ -305,7 +305,8 @@ class _EngineBase:
         plan = self._plan = self._plan_for(B, H, W, train)
         if self._needs_act16 and not plan.act16:
             raise PnnpError(f'frame {H} x {W} is too large for float32 activation maps (one image of a map must stay below 2 GB) and this forward has no fp16 '
-                            f'storage (ConvPolicy.h1_act16 takes effect in UNet eval plans whose layers all run on fp16x1): run the frame in tiles (forward_tiled)')
+                            f'storage (ConvPolicy.h1_act16 -- for ResUnet with ConvPolicy.h1_act16_res -- takes effect in eval plans whose layers all run on fp16x1): '
+                            f'run the frame in tiles (forward_tiled)')
         self._packs_ready(train, dev, plan)
         key = (B, H, W, dev)
         self._begin_forward(key, train)
@@ -339,8 +340,8 @@ class _EngineBase:
         return [dict(name=n, amax=v, overflow=65504.0 < v < float('inf'), inherited=v == float('inf')) for n, v in zip(names, vals)]
 
     def _forward_end(self, a, key, plan, T):
-        if plan.act16:                         # the stored fp16 maps' slots, by layer (conv9_2's map is never stored: the head is in its epilogue)
-            names = [n for n in plan.steps if n not in ('conv9_2', 'conv10_1')]
+        if plan.act16:                         # the stored fp16 maps' slots, by layer (conv9_2's map is never stored: the head is in its epilogue; ResUnet's head writes float32)
+            names = [n for n in plan.steps if n not in ('conv9_2', 'conv10_1', 'conv10')]
             self._act16_last = (names, [T.slot(n) for n in names])
         if plan.train:
             a['_plan'] = plan
@@ -394,9 +395,13 @@ class _EngineBase:
         fam, var = self._fam(s.fwd)
         f16 = fam in ('h2', 'h1')                            # both fp16 families: one arm, the family picks the ops wrapper (h1: eval plans only)
         if plan.act16:                                       # fp16 storage: every layer is 'h1...'; the element types are the tensors' dtypes (x8 alone is float32)
-            assert residual is None and fill is None, 'an fp16-storage plan has no residual layer and every source comes with its slot'
+            if fill is not None and x1.dtype == torch.float32:      # (ResUnet's x8 on the matrix-core first layer: a launch of its own fills the slot)
+                T.put(x1, fill, fused=False)
             ax1 = T.of(x1) if x1.dtype == torch.float32 else None
-            if var == 'splitk':
+            if residual is not None:                         # (ResUnet: an fp16 shortcut added to the float32 sum before the one rounding)
+                assert var == '', 'a residual layer is a plain launch'
+                ops.conv_h1a_fwd(x1, x2, f, wslot, bias, y, cout, act, amax_x1=ax1, amax_y=T.slot(name), residual=residual)
+            elif var == 'splitk':
                 ops.conv_h1a_fwd_splitk(x1, x2, f, wslot, bias, y, cout, act, s.ks, T.bufs.scratch('splitk_ws', s.ks * y.numel(), T.dev), amax_x1=ax1, amax_y=T.slot(name))
             else:
                 ops.conv_h1a_fwd(x1, x2, f, wslot, bias, y, cout, act, amax_x1=ax1, amax_y=T.slot(name))
@@ -425,6 +430,9 @@ class _EngineBase:
         # the first layer on the streaming kernel: its 4 input channels are not worth a (padded) GEMM chunk.  (With the fp16x2 family the
         # matrix-core kernel is as fast -- a padded chunk is 14 instructions, not 27 -- and writes the sign bits that make the next layer's
         # backward-data read 1/32 of the bytes: the streaming kernel keeps the first layer's weight gradient only.)
+        if plan.act16:                         # (fp16 storage: float16(y) out of the streaming kernel, max |y| of the float32 value into the slot)
+            ops.first_fwd_et(x, w, bias, y, act, amax_y=T.slot(name))
+            return T.put(y, name, fused=True)
         ops.first_fwd(x, w, bias, y, act, amax_y=T.slot(name) if plan.h2 else None)
         return T.put(y, name, fused=True)
 
@@ -475,7 +483,10 @@ class _EngineBase:
 
     def _head_fwd(self, plan, name, T, x, w, bias, out, res):
         """the 1x1 head on its own: x (NHWC) -> out (NCHW, + res)"""
-        if plan[name].fwd == 'thin':
+        if plan.act16 and x.dtype == torch.float16:      # (ResUnet's fp16 c9: the streaming head widens it, or the 1x1 GEMM below would need a float32 copy)
+            assert plan[name].fwd == 'thin', 'an fp16-storage plan has its head on the streaming kernel'
+            ops.head_fwd_et(x, w, bias, out, residual=res)
+        elif plan[name].fwd == 'thin':
             ops.head_fwd(x, w, bias, out, residual=res)
         else:
             o = ops.conv_fwd(x, None, self._wp[name][0], bias, T.bufs.get('o', tuple(x.shape[:3]) + (self.cout,), T.dev), self.cout, 1, 0)
@@ -554,6 +565,9 @@ class _EngineBase:
     def _s2_fwd(self, plan, name, T, x, bias, y, cout):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
+        if plan.act16:
+            ops.conv_s2_h1a_fwd(x, f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
+            return T.put(y, name, fused=True)
         if fam in ('h2', 'h1'):                              # ('h1': eval plans only, ConvPolicy.h1_pointwise)
             self._op(f'conv_s2_{fam}_fwd')(x, T.of(x), f, wslot, bias, y, cout, 0, amax_y=T.slot(name))
         elif fam == 'x3':
@@ -587,6 +601,9 @@ class _EngineBase:
     def _conv1_fwd(self, plan, name, T, x1, x2, bias, y, cout, act):
         f, _, wslot = self._wp[name]
         fam = plan[name].fwd
+        if plan.act16:                         # (its amax slot: what act16_range reports for the shortcut map)
+            ops.conv1x1_h1a_fwd(x1, x2, f, wslot, bias, y, cout, act, amax_y=T.slot(name))
+            return T.put(y, name, fused=True)
         if fam in ('h2', 'h1'):
             self._op(f'conv1x1_{fam}_fwd')(x1, T.of(x1), x2, T.of(x2), f, wslot, bias, y, cout, act)
         elif fam == 'x3':

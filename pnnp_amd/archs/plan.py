@@ -55,13 +55,16 @@ class ConvPolicy:
         # layers all resolved to 'h1...' / 'fused' (Plan.act16; csrc/conv_h1s.hip H1a, csrc/gemm_h1s.hip H1ga): float16(y) of the float32 value, unscaled, not
         # saturated.  In every other case -- ResUnet, a layer held on another family, a training plan -- it changes nothing.
         self.h1_act16 = bool(h2) and os.environ.get('PNNP_H1_ACT16', '0') != '0'
+        # (opt-in, off by default) ... and, with ALL THREE, the same storage in a ResUnet eval forward (residual sums, stride-2 and 1x1 layers and the two streaming
+        # layers at the ends included: 31 maps).  A switch of its own because ``h1_act16`` is pinned to leave ResUnet on the fp16_all plan.  UNet plans never read it.
+        self.h1_act16_res = bool(h2) and os.environ.get('PNNP_H1_ACT16_RES', '0') != '0'
 
     def key(self):
         return (self.wino, self.wino_wgrad, self.wino_mink, self.x3, self.thin, self.pool_fused, self.h2, self.h2_wgrad, self.h2_pointwise, self.head_fused, self.splitk, self.convt_bits)
 
     def plan_key(self):
         """What a cached Plan depends on: key() (the families and packs) + the switches that only change the launch sequence."""
-        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval, self.h1_pointwise, self.h1_act16)
+        return self.key() + (self.unpool_fused, self.unpool_levels, self.h1_eval, self.h1_pointwise, self.h1_act16, self.h1_act16_res)
 
     def use_thin_head(self, cin, cout, npix):
         return self.thin and ops.head_supported(cin, cout, npix)
@@ -138,7 +141,7 @@ class Plan:
     def __init__(self, steps, pol, train, ws):
         self.steps, self.pol, self.train, self.ws = steps, pol, train, ws
         self.h2 = any(p == 'h2' for s in steps.values() for p in s.pack)
-        self.act16 = False                  # (UNet eval plans under ConvPolicy.h1_act16) conv, pooled and up-sampled maps are stored as fp16: mark_act16()
+        self.act16 = False                  # (eval plans under ConvPolicy.h1_act16 / h1_act16_res) the maps convolutions write and read are stored as fp16: mark_act16()
         # the weight packs the engines build; they depend on the policy and the mode only, never on B, H, W
         self.packs = tuple(s.pack for s in steps.values())
 
@@ -163,6 +166,13 @@ class Plan:
         'fused' into one): a map has one element type, so one layer on another family keeps the whole plan on float32 storage -- the fp16_all plan, unchanged.
         The launch sequence is the same either way: families, variants and K slices stay."""
         self.act16 = not self.train and all(s.fwd == 'fused' or s.fwd.split('+')[0] == 'h1' for s in self.steps.values())
+        return self
+
+    def mark_act16_res(self, ends):
+        """(ResUnet eval plans, ConvPolicy.h1_eval + h1_pointwise + h1_act16 + h1_act16_res) the same, where the layers ``ends`` (the first layer and the head)
+        may also run on the streaming kernels ('thin': they have an fp16 side of their own, csrc/thin.hip).  A head on 'direct', or any layer on another
+        family, keeps the fp16_all plan."""
+        self.act16 = not self.train and all(s.fwd == 'h1' or (n in ends and s.fwd == 'thin') for n, s in self.steps.items())
         return self
 
     # (kind, K, N) of a pointwise forward GEMM that stays on fp16x2 under h1_pointwise because one piece measured SLOWER there (none so far)
@@ -327,6 +337,8 @@ def resolve_resunet(ch, cin, cout, pol, train, B, H, W):
                 pw.update({f'sc{i}': ('1x1', ch[9 - i], ch[9 - i]) for i in range(6, 10)})          # (K per segment of cat([up, skip]))
                 pw.update({f'pool{i}': ('s2', ch[i - 1], ch[i]) for i in range(1, 5)})             # (K per tap segment)
                 plan.to_h1_pointwise(pw)
+                if pol.h1_act16 and pol.h1_act16_res:
+                    plan.mark_act16_res(('conv_in', 'conv10'))
         return plan
     for l in range(1, 6):
         st[f'b{l}_0'].dgrad += '+res'                  # identity shortcut: d/d(input) = dgrad(block) + g in one kernel

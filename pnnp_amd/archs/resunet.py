@@ -80,10 +80,12 @@ class ResUnetEngine(_EngineBase):
         x, key, plan, bufs, P, T = self._forward_begin(x, train, reflect_pad, add_residual, tile_src)
         B, H, Wd, dev = key
         ch = self.ch
-        g = lambda n, s: bufs.get(n, s, dev)
+        g0 = lambda n, s: bufs.get(n, s, dev)
+        # (Plan.act16: the 31 maps t, c, d, u, sc are fp16 buffers, keyed apart from the float32 ones; x8 and the output stay float32)
+        g = (lambda n, s: bufs.get(n, s, dev, torch.float16)) if plan.act16 else g0
         hs = [H >> i for i in range(5)]; ws = [Wd >> i for i in range(5)]
         a = {}
-        a['x8'], x = self._layout_in(x, g('x8', (B, H, Wd, self.cin_pad)), reflect_pad, None, tile_src, bufs, dev)
+        a['x8'], x = self._layout_in(x, g0('x8', (B, H, Wd, self.cin_pad)), reflect_pad, None, tile_src, bufs, dev)
 
         def cf(name, src, src2, out, cout, act, residual=None):
             return self._conv3_fwd(plan, name, T, a, src, src2, None, out, cout, act, residual=residual)

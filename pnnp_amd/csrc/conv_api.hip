@@ -221,7 +221,8 @@ int convt_fwd(const F16Family& f, const float* x, int Cin, const unsigned* amax_
 
 int conv1x1_fwd(const F16Family& f, const float* x1, int C1, const unsigned* amax_x1, const float* x2, int C2, const unsigned* amax_x2, const void* w, const unsigned* amax_w,
                 const float* bias, const float* residual, float* y, unsigned* amax_y, int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x1 || !w || !y || !amax_x1 || !amax_w || (x2 && !amax_x2) || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (!x1 || !w || !y || !amax_w || !f.pointwise || B < 0 || H <= 0 || W <= 0 || C1 <= 0 || (x2 && C2 != C1)) return PNNP_E_INVALID;
+    if (!f.src_f16 && (!amax_x1 || (x2 && !amax_x2))) return PNNP_E_INVALID;                  // (an fp16 source has no slot)
     if (B == 0) return PNNP_OK;
     H2Args h{};
     fwd_args(h.g, x1, C1, x2, C2, w, bias, residual, y, B, H, W, Cout, act);
@@ -231,7 +232,7 @@ int conv1x1_fwd(const F16Family& f, const float* x1, int C1, const unsigned* ama
 
 int conv_s2_fwd(const F16Family& f, const float* x, int Cin, const unsigned* amax_x, const void* w, const unsigned* amax_w, const float* bias, float* y, unsigned* amax_y,
                 int B, int H, int W, int Cout, int act, void* stream) {
-    if (!x || !w || !y || !amax_x || !amax_w || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
+    if (!x || !w || !y || (!amax_x && !f.src_f16) || !amax_w || !f.pointwise || B < 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return PNNP_E_INVALID;
     if (B == 0) return PNNP_OK;
     H2Args h{};
     s2_fwd_args(h.g, x, Cin, w, bias, y, B, H, W, Cout, act);
@@ -456,6 +457,30 @@ int pnnp_conv3x3_h1_fwd_pool_et(const void* x1, int C1, const unsigned* amax_x1,
                                 int act, void* stream) {
     return conv3_fwd_pool(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, (float*)y, (float*)pooled, codes,
                           amax_y, nullptr, B, H, W, Cout, act, stream);
+}
+
+// ... with a RESIDUAL: fp16 sources, an fp16 residual of y's geometry and an fp16 y (csrc/conv_s_body.h EK_RES with DST16): y16 = float16((acc 2^dexp + bias) + float(r16)),
+// one rounding; amax_y the float32 sum.  All three flags 0: the _f32 entry.  A mixed triple has no kernel.
+int pnnp_conv3x3_h1_fwd_res_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                               const float* bias, const void* residual, void* y, unsigned* amax_y, int src_f16, int res_f16, int dst_f16, int B, int H, int W, int Cout,
+                               int act, void* stream) {
+    if (!residual) return PNNP_E_INVALID;
+    if (!src_f16 != !dst_f16 || !res_f16 != !dst_f16) return PNNP_E_UNSUPPORTED;
+    return conv3_fwd(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, (const float*)residual, (float*)y,
+                     amax_y, nullptr, B, H, W, Cout, act, stream);
+}
+// the stride-2 3x3 layer and the 1x1 layer on cat([x1, x2]) of an fp16-storage forward (csrc/gemm_h1s.hip H1ga): x and y fp16, or the _f32 twin; a mixed pair: PNNP_E_UNSUPPORTED
+int pnnp_conv_s2_h1_fwd_et(const void* x, int Cin, const unsigned* amax_x, const void* w_h1, const unsigned* amax_w, const float* bias, void* y, unsigned* amax_y,
+                           int src_f16, int dst_f16, int B, int H, int W, int Cout, int act, void* stream) {
+    if (!src_f16 != !dst_f16) return PNNP_E_UNSUPPORTED;
+    return conv_s2_fwd(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x, Cin, amax_x, w_h1, amax_w, bias, (float*)y, amax_y, B, H, W, Cout, act, stream);
+}
+int pnnp_conv1x1_h1_fwd_et(const void* x1, int C1, const unsigned* amax_x1, const void* x2, int C2, const unsigned* amax_x2, const void* w_h1, const unsigned* amax_w,
+                           const float* bias, const float* residual, void* y, unsigned* amax_y, int src_f16, int dst_f16, int B, int H, int W, int Cout, int act,
+                           void* stream) {
+    if (!src_f16 != !dst_f16 || (src_f16 && residual)) return PNNP_E_UNSUPPORTED;
+    return conv1x1_fwd(FAM_H1A[!!src_f16][!!dst_f16], (const float*)x1, C1, amax_x1, (const float*)x2, C2, amax_x2, w_h1, amax_w, bias, residual, (float*)y, amax_y,
+                       B, H, W, Cout, act, stream);
 }
 
 // mask1 / mask2: the float32 activation, or bits1 / bits2: its sign bits from the forward kernel (then the float32 pointer is not read)

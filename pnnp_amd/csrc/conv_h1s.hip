@@ -99,11 +99,11 @@ int launch_h1s(const H2Args& a, hipStream_t s) { return conv_s_launch<H1s, BN, E
 // ---- the same scheme with fp16 ACTIVATIONS on one or both sides ("h1a": csrc/conv_s.h SElem, csrc/conv_s_body.h SRC16 / DST16).  An fp16 source is unscaled
 // (se_x = 0: its halves are the halo image's words, dexp = -se_w) and has no amax slot; an fp16 destination is float16(y) of the float32 value H1s stores, and
 // its amax slot still records max |y| BEFORE the rounding.  Same pack (kind 7), same mfma_item: fed x16 and x16.float() the two schemes add the same products
-// times the same power of two in the same order.  Split-K slabs (EK_GEN) stay float32; the residual epilogue is not offered.
+// times the same power of two in the same order.  Split-K slabs (EK_GEN) stay float32; the residual epilogue (EK_RES) exists with fp16 on all three sides only.
 template <bool S16, bool D16>
 struct H1a : H1s {
     static constexpr bool SRC16 = S16, DST16 = D16;
-    static constexpr bool has(int EK, int BN) { return D16 ? (EK == EK_FWD || EK == EK_POOL) : (EK == EK_FWD || EK == EK_GEN || (EK == EK_HEAD && BN == 32)); }
+    static constexpr bool has(int EK, int BN) { return D16 ? (EK == EK_FWD || EK == EK_POOL || (S16 && EK == EK_RES)) : (EK == EK_FWD || EK == EK_GEN || (EK == EK_HEAD && BN == 32)); }
     static __device__ __forceinline__ void scale_exps(const H2Args& ha, int& se_x, int& se_w) {
         if constexpr (S16) { se_x = 0; se_w = __builtin_amdgcn_readfirstlane(ha.amax_w ? pnnp_h2_scale_exp(ha.amax_w[0]) : 0); }
         else H1s::scale_exps(ha, se_x, se_w);
@@ -160,7 +160,7 @@ int pnnp_h1_splitk_reduce_f16_launch(const float* slab, int S, const float* bias
 
 // pnnp_igemm_h1s_launch with element types: src_f16: every K segment is an fp16 NHWC tensor (a.seg[i].ptr points at halves; cstride and coff in multiples of 8,
 // no amax slot read); dst_f16: dst[0] and the pooled map are fp16 (channel strides in multiples of 8).  Refuses what pnnp_igemm_h1s_launch refuses, and: a
-// residual, an fp16 split-K slab, a stored map beside the head.  Both zero: pnnp_igemm_h1s_launch itself.
+// residual unless all three sides are fp16, an fp16 split-K slab, a stored map beside the head.  Both zero: pnnp_igemm_h1s_launch itself.
 int pnnp_igemm_h1a_launch(const H2Args& ha, int chan_per_seg, int src_f16, int dst_f16, hipStream_t s) {
     if (!src_f16 && !dst_f16) return pnnp_igemm_h1s_launch(ha, chan_per_seg, s);
     const IgemmArgs& a = ha.g;
@@ -169,7 +169,9 @@ int pnnp_igemm_h1a_launch(const H2Args& ha, int chan_per_seg, int src_f16, int d
     if (src_f16) { b.amax_in[0] = nullptr; b.amax_in[1] = nullptr; }
     if ((((uintptr_t)b.amax_in[0]) | ((uintptr_t)b.amax_in[1]) | ((uintptr_t)ha.amax_w) | ((uintptr_t)ha.amax_out[0]) | ((uintptr_t)ha.amax_out[1])) & 3) return PNNP_E_INVALID;
     if (a.mask[0] || a.mask[1] || a.mask_mode[0] || a.mask_mode[1] || a.accum[0] || a.accum[1] || ha.bits_out || ha.bits_in[0] || ha.bits_in[1] ||
-        ha.unpool_g || ha.unpool_codes || ha.dgrad_plain || a.addsrc || a.dst[1]) return PNNP_E_UNSUPPORTED;
+        ha.unpool_g || ha.unpool_codes || ha.dgrad_plain || a.dst[1]) return PNNP_E_UNSUPPORTED;
+    // a residual (a.addsrc: an fp16 tensor of dst[0]'s geometry, read through the destination's offsets): fp16 on all three sides, the plain layer, no activation
+    if (a.addsrc && (!src_f16 || !dst_f16 || a.act || ha.ksplit > 1 || ha.head_out || a.pool_dst || a.pool_codes)) return PNNP_E_UNSUPPORTED;
     if (const int rc = conv_s_validate(a, chan_per_seg, H1s::ITEMS * H1s::WBLK, b.g, src_f16 ? 2 : 4, dst_f16 ? 2 : 4); rc != PNNP_OK) return rc;
     if (b.ksplit < 1) b.ksplit = 1;
     if (b.ksplit > 1) {
@@ -191,6 +193,7 @@ int pnnp_igemm_h1a_launch(const H2Args& ha, int chan_per_seg, int src_f16, int d
         return pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 1) == 64 ? launch_h1a<64, EK_POOL, true, true>(b, s) : launch_h1a<32, EK_POOL, true, true>(b, s);
     }
     const bool wide = pnnp_conv3_tile_columns(a.B, a.DH, a.DW, a.Ntot, 0) == 64;
+    if (a.addsrc) return wide ? launch_h1a<64, EK_RES, true, true>(b, s) : launch_h1a<32, EK_RES, true, true>(b, s);
     if (src_f16 && dst_f16) return wide ? launch_h1a<64, EK_FWD, true, true>(b, s) : launch_h1a<32, EK_FWD, true, true>(b, s);
     if (src_f16) return wide ? launch_h1a<64, EK_FWD, true, false>(b, s) : launch_h1a<32, EK_FWD, true, false>(b, s);
     return wide ? launch_h1a<64, EK_FWD, false, true>(b, s) : launch_h1a<32, EK_FWD, false, true>(b, s);

@@ -6,7 +6,7 @@
     // element types of the activations (csrc/conv_s.h SElem): fp16 K segments / an fp16 dst[0] and pooled map; LPS: 16-byte loads per staging slot (8 channels)
     constexpr bool SRC16 = SElem<Scheme>::SRC16, DST16 = SElem<Scheme>::DST16;
     constexpr int SRC_ES = SRC16 ? 2 : 4, LPS = SRC16 ? 1 : 2;
-    static_assert(!DST16 || EK == EK_FWD || EK == EK_POOL || EK == EK_HEAD, "epilogues with an fp16 destination");
+    static_assert(!DST16 || EK == EK_FWD || EK == EK_POOL || EK == EK_HEAD || (EK == EK_RES && SRC16), "epilogues with an fp16 destination");
     using Cfg = SCfg<Scheme, BN>;
     constexpr int NT = Cfg::NT, D = Cfg::DPW, XS_F4 = Cfg::XS_F4, XS_BYTES = Cfg::XS_BYTES, NSTAGE = Cfg::NSTAGE, AHEAD = Cfg::AHEAD, ITEMS = Scheme::ITEMS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -672,9 +672,20 @@
         if constexpr (EK == EK_FWD || EK == EK_BWD || EK == EK_BWDB || EK == EK_HEAD || EK == EK_RES || EK == EK_BWDU) {
             constexpr bool RES = EK == EK_RES, UNP = EK == EK_BWDU;
             constexpr bool MASKED = EK == EK_BWD, BITS = EK == EK_BWDB || UNP, FWDL = EK == EK_FWD || EK == EK_HEAD;
-            f32x4 mk[(MASKED || RES) ? MB : 1][(MASKED || RES) ? NB : 1];      // [.][2 k] = what instruction 1 fetched, [.][2 k + 1] = instruction 2 (EK_RES: the residual words)
+            constexpr bool RES16 = RES && DST16;                  // an fp16 residual beside the fp16 destination: one 16-byte word per store instruction
+            f32x4 mk[((MASKED || RES) && !RES16) ? MB : 1][((MASKED || RES) && !RES16) ? NB : 1];      // [.][2 k] = what instruction 1 fetched, [.][2 k + 1] = instruction 2 (EK_RES: the residual words)
+            u32x4 mk16[RES16 ? MB : 1][RES16 ? NT : 1];            // (RES16) the residual's eight halves at the store's own offset: the post-swap arrangement of pack16
             unsigned mbits[NT];
-            if constexpr (MASKED || RES) {
+            if constexpr (RES16) {
+#pragma unroll
+                for (int k = 0; k < NT; ++k) {
+                    const __amdgpu_buffer_rsrc_t rm = rsrc16(ea.addsrc, k);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) mk16[2 * i + h][k] = __builtin_amdgcn_raw_buffer_load_b128(rm, wo16[k][i][h], 0, 0);
+                }
+            } else if constexpr (MASKED || RES) {
 #pragma unroll
                 for (int k = 0; k < NT; ++k) {
                     const int mm = RES ? 1 : ea.mask_mode(du_[k]);
@@ -734,7 +745,21 @@
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) { o0[c] = q0[c] > 0.f ? o0[c] : t0[c]; o1[c] = q1[c] > 0.f ? o1[c] : t1[c]; }
                             }
-                            if constexpr (RES) {                       // trade first, then add what the two store instructions' addresses hold of the residual
+                            if constexpr (RES16) {
+                                // the residual word holds the halves as pack16 leaves them: the swap is an involution, so swapping its dwords back gives this lane's
+                                // own two quads (lower / upper 16-column block); widened exactly, added to the float32 sums, then ONE rounding in pack16
+                                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+                                const u32x4 rw = mk16[2 * i + h][k];
+                                const auto u0 = __builtin_amdgcn_permlane16_swap(rw.x, rw.z, false, false), u1 = __builtin_amdgcn_permlane16_swap(rw.y, rw.w, false, false);
+                                const f16x2 r00 = __builtin_bit_cast(f16x2, (unsigned)u0[0]), r01 = __builtin_bit_cast(f16x2, (unsigned)u1[0]);
+                                const f16x2 r10 = __builtin_bit_cast(f16x2, (unsigned)u0[1]), r11 = __builtin_bit_cast(f16x2, (unsigned)u1[1]);
+                                o0 += f32x4{(float)r00.x, (float)r00.y, (float)r01.x, (float)r01.y};
+                                o1 += f32x4{(float)r10.x, (float)r10.y, (float)r11.x, (float)r11.y};
+                                track(o0); track(o1);
+                                __builtin_amdgcn_raw_buffer_store_b128(pack16(o0, o1), rd, wo16[k][i][h], 0, CONVS_STORE_AUX);
+                                __builtin_amdgcn_sched_barrier(0);
+                                continue;
+                            } else if constexpr (RES) {                // trade first, then add what the two store instructions' addresses hold of the residual
                                 trade(o0, o1);
                                 o0 += mk[2 * i + h][2 * k]; o1 += mk[2 * i + h][2 * k + 1];
                                 track(o0); track(o1);

@@ -21,6 +21,7 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
@@ -41,7 +42,9 @@ struct HeadFwd {
     int64_t npix, hw; int xcs, cin, cout;
 };
 
-template <int LPP>
+// X16: x is an fp16 NHWC tensor behind a.x (the fp16-storage eval forward of ResUnet): the lane's four channels are one 8-byte load, widened (exact), then the
+// same products and sums in the same order -- fed x16 it gives bit for bit what the float32 kernel gives fed float(x16)
+template <int LPP, bool X16 = false>
 __global__ void __launch_bounds__(256)
 head_fwd_kernel(HeadFwd a) {
     constexpr int PPI = 64 / LPP;              // pixels per wave instruction
@@ -59,8 +62,14 @@ head_fwd_kernel(HeadFwd a) {
         const int64_t base = grp << 6;
         f32x4 xv[LPP];
 #pragma unroll
-        for (int k = 0; k < LPP; ++k)
-            xv[k] = *reinterpret_cast<const f32x4*>(a.x + (base + k * PPI + p) * a.xcs + 4 * q);
+        for (int k = 0; k < LPP; ++k) {
+            if constexpr (X16) {
+                const f16x4 hv = *reinterpret_cast<const f16x4*>(reinterpret_cast<const _Float16*>(a.x) + (base + k * PPI + p) * a.xcs + 4 * q);
+                xv[k] = f32x4{(float)hv.x, (float)hv.y, (float)hv.z, (float)hv.w};
+            } else {
+                xv[k] = *reinterpret_cast<const f32x4*>(a.x + (base + k * PPI + p) * a.xcs + 4 * q);
+            }
+        }
         float keep[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < LPP; ++k) {
@@ -300,9 +309,11 @@ struct FirstF {
     unsigned* amax;                     // max |y| (csrc/h2.h) or null
 };
 
-template <int CO>
+// Y16: y is an fp16 NHWC tensor behind a.y: float16(v) of the float32 value, one round to nearest even, not saturated; the amax slot takes |v| before the rounding
+template <int CO, bool Y16 = false>
 __global__ void __launch_bounds__(256)
 first_fwd_kernel(FirstF a) {
+    using TY = std::conditional_t<Y16, _Float16, float>;
     constexpr int NS = 256 / CO, TR = 2 * NS;
     constexpr int NX = (TR + 2) * FW_LW, NLD = (NX + 255) / 256;
     __shared__ f32x4 xt[NX];
@@ -338,8 +349,8 @@ first_fwd_kernel(FirstF a) {
         for (int k = 0; k < NLD; ++k)
             if (threadIdx.x + 256 * k < NX) xt[threadIdx.x + 256 * k] = stage[k];
         __syncthreads();
-        float* y0 = a.y + (((int64_t)b * a.H + h0 + 2 * st) * a.W + w0) * a.ycs + co;
-        float* y1 = y0 + (int64_t)a.W * a.ycs;
+        TY* y0 = reinterpret_cast<TY*>(a.y) + (((int64_t)b * a.H + h0 + 2 * st) * a.W + w0) * a.ycs + co;
+        TY* y1 = y0 + (int64_t)a.W * a.ycs;
         const f32x4* xr = xt + 2 * st * FW_LW;
         f32x4 s0[4], s1[4], s2[4];               // window columns; slot = (tile column + 1) % 3
 #pragma unroll
@@ -357,7 +368,7 @@ first_fwd_kernel(FirstF a) {
                 }
                 float v = (acc[0] + acc[1]) + bs;
                 v = fmaxf(v, slope * v);
-                if (col < nw) { (row ? y1 : y0)[(int64_t)col * a.ycs] = v; amx = fmaxf(amx, fabsf(v)); }
+                if (col < nw) { (row ? y1 : y0)[(int64_t)col * a.ycs] = (TY)v; amx = fmaxf(amx, fabsf(v)); }
             }
         };
         for (int w = 0; w < FW_TW; w += 3) {
@@ -426,12 +437,26 @@ int64_t pnnp_head_bwd_workspace_floats(int cin) { return (int64_t)pnnp_device_cu
 
 int pnnp_head_fwd_f32(const float* x, int xcs, int cin, const float* w, const float* bias, const float* residual, float* out,
                       int B, int H, int W, int cout, void* stream) {
+    return pnnp_head_fwd_et(x, xcs, cin, w, bias, residual, out, 0, B, H, W, cout, stream);
+}
+// ... with the element type of x: src_f16 != 0: x is an fp16 NHWC tensor (8-byte loads: x 8-byte aligned, xcs in multiples of 4), widened exactly; w, bias,
+// residual and out stay float32.  Fed x16 where the entry above is fed float(x16) the outputs agree bit for bit.
+int pnnp_head_fwd_et(const void* x, int xcs, int cin, const float* w, const float* bias, const float* residual, float* out, int src_f16,
+                     int B, int H, int W, int cout, void* stream) {
     const int64_t npix = (int64_t)B * H * W;
-    if (!x || !w || !bias || !out || B < 0 || H <= 0 || W <= 0 || (xcs & 3) || xcs < cin) return PNNP_E_INVALID;
+    if (!x || !w || !bias || !out || B < 0 || H <= 0 || W <= 0 || (xcs & 3) || xcs < cin || (src_f16 && (((uintptr_t)x) & 7))) return PNNP_E_INVALID;
     if (B == 0) return PNNP_OK;
     if (!pnnp_head_supported(cin, cout, npix)) return PNNP_E_UNSUPPORTED;
-    HeadFwd a{x, w, bias, residual, out, npix, (int64_t)H * W, xcs, cin, cout};
+    HeadFwd a{static_cast<const float*>(x), w, bias, residual, out, npix, (int64_t)H * W, xcs, cin, cout};
     const dim3 grid(thin_blocks((npix >> 6) / 4, 8)), blk(256);
+    if (src_f16) {
+        switch (head_lpp(cin)) {
+            case 4: hipLaunchKernelGGL((head_fwd_kernel<4, true>), grid, blk, 0, as_stream(stream), a); break;
+            case 8: hipLaunchKernelGGL((head_fwd_kernel<8, true>), grid, blk, 0, as_stream(stream), a); break;
+            default: hipLaunchKernelGGL((head_fwd_kernel<16, true>), grid, blk, 0, as_stream(stream), a); break;
+        }
+        return pnnp_launch_status();
+    }
     switch (head_lpp(cin)) {
         case 4: hipLaunchKernelGGL(head_fwd_kernel<4>, grid, blk, 0, as_stream(stream), a); break;
         case 8: hipLaunchKernelGGL(head_fwd_kernel<8>, grid, blk, 0, as_stream(stream), a); break;
@@ -508,13 +533,24 @@ int pnnp_first_fwd_f32(const float* x, int xcs, int cin, const float* w, const f
 // ... and max |y| into an amax slot (csrc/h2.h)
 int pnnp_first_fwd_amax_f32(const float* x, int xcs, int cin, const float* w, const float* bias, float* y, int ycs, int B, int H, int W, int cout,
                             int act, unsigned* amax_y, void* stream) {
+    return pnnp_first_fwd_amax_et(x, xcs, cin, w, bias, y, ycs, B, H, W, cout, act, amax_y, 0, stream);
+}
+// ... with the element type of y: dst_f16 != 0: y is an fp16 NHWC tensor = float16(the float32 value the entry above stores), one round to nearest even, unscaled,
+// not saturated; amax_y still records max |.| of the float32 value.  x stays float32 (the network input's zero-padded NHWC copy).
+int pnnp_first_fwd_amax_et(const float* x, int xcs, int cin, const float* w, const float* bias, void* y, int ycs, int B, int H, int W, int cout,
+                           int act, unsigned* amax_y, int dst_f16, void* stream) {
     if (!x || !w || !y || B < 0 || H <= 0 || W <= 0 || (xcs & 3) || xcs < 4 || ycs < cout || act < 0 || act > 2) return PNNP_E_INVALID;
     if (B == 0) return PNNP_OK;
     if (!pnnp_first_wgrad_supported(cin, cout, H, W)) return PNNP_E_UNSUPPORTED;
     const int tr = 512 / cout;
-    FirstF a{x, w, bias, y, B, H, W, xcs, ycs, cin, act, ceil_div(W, FW_TW), 0, amax_y};
+    FirstF a{x, w, bias, static_cast<float*>(y), B, H, W, xcs, ycs, cin, act, ceil_div(W, FW_TW), 0, amax_y};
     a.ntiles = B * (H / tr) * a.tiles_w;
     const dim3 grid(thin_blocks(a.ntiles, FW_PER_CU)), blk(256);
+    if (dst_f16) {
+        if (cout == 32) hipLaunchKernelGGL((first_fwd_kernel<32, true>), grid, blk, 0, as_stream(stream), a);
+        else hipLaunchKernelGGL((first_fwd_kernel<64, true>), grid, blk, 0, as_stream(stream), a);
+        return pnnp_launch_status();
+    }
     if (cout == 32) hipLaunchKernelGGL(first_fwd_kernel<32>, grid, blk, 0, as_stream(stream), a);
     else hipLaunchKernelGGL(first_fwd_kernel<64>, grid, blk, 0, as_stream(stream), a);
     return pnnp_launch_status();

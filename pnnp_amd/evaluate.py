@@ -31,6 +31,8 @@ _PRECISION = {'fp32': dict(h1_eval=False), 'fp16': dict(h1_eval=True), 'fp16_all
 # ... and the precisions that also choose how activations are STORED.  A table of its own for one reason only: tests/test_host_h1pw_ref.py pins _PRECISION to
 # exactly the three entries above, and existing tests stay as they are.  _precision() reads both; a later change that may touch that test can merge them.
 _PRECISION_STORAGE = {'fp16_act': dict(h1_eval=True, h1_pointwise=True, h1_act16=True)}
+# ... and fp16 storage for ResUnet as well (ConvPolicy.h1_act16_res).  A third table for the same reason: tests/test_host_act16_ref.py pins the one above.
+_PRECISION_STORAGE_RES = {'fp16_act_res': dict(h1_eval=True, h1_pointwise=True, h1_act16=True, h1_act16_res=True)}
 
 
 @contextlib.contextmanager
@@ -41,13 +43,15 @@ def _precision(net, precision):
     alternating precisions per call re-packs each time -- to serve one precision, call ``net.engine.set_policy(h1_eval=True)`` once instead.
     'fp16_all' is 'fp16' with the ConvTranspose2d / 1x1 / stride-2 layers on one fp16 piece as well (ConvPolicy.h1_pointwise, csrc/gemm_h1s.hip): both
     switches are set for the call and both come back.  'fp16_act' is 'fp16_all' with every map a convolution writes and a convolution reads STORED as fp16
-    (ConvPolicy.h1_act16; UNet plans whose layers all run on fp16x1 -- otherwise it is 'fp16_all'): three switches, set and restored alike."""
+    (ConvPolicy.h1_act16; UNet plans whose layers all run on fp16x1 -- otherwise it is 'fp16_all'): three switches, set and restored alike.
+    'fp16_act_res' is 'fp16_act' that reaches ResUnet too (ConvPolicy.h1_act16_res: its residual sums, stride-2 and 1x1 layers and both ends read and write
+    fp16): four switches; on a UNet it is 'fp16_act' bit for bit."""
     if precision is None:
         yield
         return
-    want = _PRECISION.get(precision) or _PRECISION_STORAGE.get(precision)
+    want = _PRECISION.get(precision) or _PRECISION_STORAGE.get(precision) or _PRECISION_STORAGE_RES.get(precision)
     if want is None:
-        raise PnnpError(f"precision must be None, 'fp32', 'fp16', 'fp16_all' or 'fp16_act', got {precision!r}")
+        raise PnnpError(f"precision must be None, 'fp32', 'fp16', 'fp16_all', 'fp16_act' or 'fp16_act_res', got {precision!r}")
     eng = getattr(net, 'engine', None)
     if eng is None or not hasattr(eng, 'set_policy'):
         if precision != 'fp32':

@@ -564,12 +564,20 @@ def _h1a_bytes(B, H, W, C1, C2, cout, s16, d16):
     return B * H * W * ((C1 + C2) * (2.0 if s16 else 4.0) + cout * (2.0 if d16 else 4.0))
 
 
-def conv_h1a_fwd(x1, x2, w, amax_w, bias, y, cout, act, amax_x1=None, amax_x2=None, amax_y=None):
-    """conv_h1_fwd with the element types of ``x1`` / ``x2`` and ``y`` (no residual)"""
-    s16, d16 = _h1a_types('conv_h1a_fwd', x1, x2, y)
-    require_cuda(x1, x2, w, y, amax_w)
+def conv_h1a_fwd(x1, x2, w, amax_w, bias, y, cout, act, amax_x1=None, amax_x2=None, amax_y=None, residual=None):
+    """conv_h1_fwd with the element types of ``x1`` / ``x2`` and ``y``.  ``residual`` (pnnp_conv3x3_h1_fwd_res_et): a tensor of y's shape and dtype, added to
+    the float32 sum before the one rounding; offered with torch.float16 on all three sides (float32 on all three: conv_h1_fwd), no activation."""
+    s16, d16 = _h1a_types('conv_h1a_fwd', x1, x2, y, residual)
+    require_cuda(x1, x2, w, y, amax_w, residual)
     B, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
+    if residual is not None:
+        if tuple(residual.shape) != tuple(y.shape):
+            raise _lib.PnnpError(f'conv_h1a_fwd: the residual is {tuple(residual.shape)}, y {tuple(y.shape)}')
+        with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9, _h1a_bytes(B, H, W, C1, C2, 2 * cout, s16, d16), sub=lambda: 'res_bn%d' % h2_tile_columns(B, H, W, cout)):
+            check(_prep().pnnp_conv3x3_h1_fwd_res_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(residual), ptr(y),
+                                                     ptr(amax_y), s16, d16, d16, B, H, W, cout, act, stream()), 'conv_h1a_fwd')
+        return y
     with _Timed('conv9_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2) * 9, _h1a_bytes(B, H, W, C1, C2, cout, s16, d16), sub=lambda: 'bn%d' % h2_tile_columns(B, H, W, cout)):
         check(_prep().pnnp_conv3x3_h1_fwd_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16,
                                              B, H, W, cout, act, stream()), 'conv_h1a_fwd')
@@ -732,6 +740,29 @@ def convt_h1a_fwd(x, w, amax_w, bias, y, cout, amax_x=None, amax_y=None):
     B, H, W, Cin = x.shape
     with _Timed('convt_fwd_h1a', 8.0 * B * H * W * Cin * cout, B * H * W * ((2.0 if s16 else 4.0) * Cin + (2.0 if d16 else 4.0) * 4 * cout)):
         check(_prep().pnnp_convt_h1_fwd_et(ptr(x), Cin, ptr(amax_x), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16, B, H, W, cout, stream()), 'convt_h1a_fwd')
+    return y
+
+
+def conv_s2_h1a_fwd(x, w, amax_w, bias, y, cout, act, amax_x=None, amax_y=None):
+    """conv_s2_h1_fwd with the element types of ``x`` and ``y`` (csrc/gemm_h1s.hip H1ga): both torch.float16 or both float32; a mixed pair is refused by the entry"""
+    s16, d16 = _h1a_types('conv_s2_h1a_fwd', x, None, y)
+    require_cuda(x, w, y, amax_w)
+    B, H, W, Cin = x.shape
+    with _Timed('conv9s2_fwd_h1a', 2.0 * B * (H // 2) * (W // 2) * cout * Cin * 9, B * H * W * ((2.0 if s16 else 4.0) * Cin + (2.0 if d16 else 4.0) * cout / 4)):
+        check(_prep().pnnp_conv_s2_h1_fwd_et(ptr(x), Cin, ptr(amax_x), ptr(w), ptr(amax_w), ptr(bias), ptr(y), ptr(amax_y), s16, d16, B, H, W, cout, act, stream()),
+              'conv_s2_h1a_fwd')
+    return y
+
+
+def conv1x1_h1a_fwd(x1, x2, w, amax_w, bias, y, cout, act, amax_x1=None, amax_x2=None, amax_y=None):
+    """conv1x1_h1_fwd on cat([x1, x2]) with the element types of the sources and ``y``: all torch.float16 or all float32; no residual"""
+    s16, d16 = _h1a_types('conv1x1_h1a_fwd', x1, x2, y)
+    require_cuda(x1, x2, w, y, amax_w)
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    with _Timed('conv1_fwd_h1a', 2.0 * B * H * W * cout * (C1 + C2), _h1a_bytes(B, H, W, C1, C2, cout, s16, d16)):
+        check(_prep().pnnp_conv1x1_h1_fwd_et(ptr(x1), C1, ptr(amax_x1), ptr(x2), C2, ptr(amax_x2), ptr(w), ptr(amax_w), ptr(bias), ptr(None), ptr(y), ptr(amax_y), s16, d16,
+                                             B, H, W, cout, act, stream()), 'conv1x1_h1a_fwd')
     return y
 
 
@@ -1086,6 +1117,22 @@ def head_fwd(x, weight, bias, out, residual=None):
     return out
 
 
+def head_fwd_et(x, weight, bias, out, residual=None):
+    """head_fwd with the element type of ``x``: a torch.float16 NHWC map is widened exactly in the kernel; everything else stays float32"""
+    if x.dtype not in (torch.float16, torch.float32):
+        raise _lib.PnnpError(f'head_fwd_et: x is {x.dtype}: torch.float16 or torch.float32')
+    for t in (weight, bias, out, residual):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.PnnpError(f'head_fwd_et: the head is float32, got {t.dtype}')
+    require_cuda(x, weight, bias, out, residual)
+    B, H, W, xcs = x.shape
+    cout, cin = weight.shape[0], weight.shape[1]
+    s16 = int(x.dtype == torch.float16)
+    with _Timed('head_fwd_et', 2.0 * B * H * W * cin * cout, B * H * W * ((2.0 if s16 else 4.0) * cin + 4.0 * cout)):
+        check(_prep().pnnp_head_fwd_et(ptr(x), xcs, cin, ptr(weight), ptr(bias), ptr(residual), ptr(out), s16, B, H, W, cout, stream()), 'head_fwd_et')
+    return out
+
+
 def head_bwd(g, x, weight, gx, dW, dbias, ws, mode=0, accumulate=0, amax_gx=None):
     """Backward of the 1x1 head in one pass: gx [B,H,W,>=cin] = (g W) * act'(x), dW [cout,cin,1,1] and dbias (+)=.
     g [B,H,W,gcs>=4] (first cout channels), x [B,H,W,>=cin] the head's input (an activation output when mode != 0)."""
@@ -1113,6 +1160,19 @@ def first_fwd(x, weight, bias, y, act, amax_y=None):
     cout, cin = weight.shape[0], weight.shape[1]
     with _Timed('first_fwd', 2.0 * B * H * W * cout * cin * 9, 4.0 * B * H * W * (cin + cout)):
         check(_prep().pnnp_first_fwd_amax_f32(ptr(x), xcs, cin, ptr(weight), ptr(bias), ptr(y), y.shape[3], B, H, W, cout, act, ptr(amax_y), stream()), 'first_fwd')
+    return y
+
+
+def first_fwd_et(x, weight, bias, y, act, amax_y=None):
+    """first_fwd with the element type of ``y``: a torch.float16 ``y`` receives float16(the float32 value first_fwd stores); ``x`` stays float32"""
+    if x.dtype != torch.float32 or y.dtype not in (torch.float16, torch.float32):
+        raise _lib.PnnpError(f'first_fwd_et: x float32 and y torch.float16 or float32, got {x.dtype} -> {y.dtype}')
+    require_cuda(x, weight, y)
+    B, H, W, xcs = x.shape
+    cout, cin = weight.shape[0], weight.shape[1]
+    d16 = int(y.dtype == torch.float16)
+    with _Timed('first_fwd_et', 2.0 * B * H * W * cout * cin * 9, B * H * W * (4.0 * cin + (2.0 if d16 else 4.0) * cout)):
+        check(_prep().pnnp_first_fwd_amax_et(ptr(x), xcs, cin, ptr(weight), ptr(bias), ptr(y), y.shape[3], B, H, W, cout, act, ptr(amax_y), d16, stream()), 'first_fwd_et')
     return y
 
 

@@ -160,15 +160,83 @@ def act16_main(a):
         f.write(text)
 
 
+def act16_res_main(a):
+    """'fp16_act_res' (ConvPolicy.h1_act16_res: fp16 storage of ResUnet's 31 maps) alternated with 'fp32' / 'fp16' / 'fp16_all' in one process; the yardstick of
+    the new column is the 'fp16_all' column of the SAME run.  ResUnet nf = 32 on 16 crops of 512 and on one crop; then the launches one by one."""
+    out = a.out
+    g = torch.Generator(device='cuda').manual_seed(1)
+    r2, r1, ra, sd = make('resunet')
+    rc = ResUnet(dict(nframes=1, res=False, nf=32, in_nc=4, out_nc=4))
+    rc.load_state_dict({k: v.clone() for k, v in sd.items()})
+    rc = rc.cuda().eval()
+    rc.engine.set_policy(h1_eval=True, h1_pointwise=True, h1_act16=True, h1_act16_res=True)
+    hr = sid_like((1, 4, H, W), g)
+    frame = (hr + 0.02 * torch.randn(1, 4, H, W, device='cuda', generator=g)).clamp(0, 1)
+    crop1 = frame[:, :, 400:912, 800:1312].contiguous()
+    crops16 = torch.cat([frame[:, :, 64 * i:64 * i + 512, 100 * i:100 * i + 512] for i in range(14)] + [crop1, crop1.flip(-1)]).contiguous()
+    L = [f"fp16 storage of ResUnet's activations ('fp16_act_res') against 'fp16_all', 'fp16' and 'fp32' on {torch.cuda.get_device_name(0)}; ResUnet nf = 32; random variance-preserving weights",
+         f'per call, median [min .. max] over {a.reps} rounds, the four modes alternated inside every round (four engines, same weights: no re-pack is timed); device events', '']
+
+    def fwd(net, x):
+        def f():
+            with torch.no_grad():
+                net.engine.forward(x, False)
+        return f
+    nets = {'fp32': r2, 'fp16': r1, 'fp16_all': ra, 'fp16_act_res': rc}
+    L.append('(a) eval forward')
+    for name, x, inner in (('16 crops 4x512x512', crops16, 4), ('1 crop 4x512x512', crop1, 20)):
+        res = rounds({k: fwd(n, x) for k, n in nets.items()}, a.reps, inner)
+        ma, mc = np.median(res['fp16_all']), np.median(res['fp16_act_res'])
+        spread = max((max(res[k]) - min(res[k])) / np.median(res[k]) for k in ('fp16_all', 'fp16_act_res'))
+        L.append(f'  {name}')
+        for k in nets:
+            L.append(f'    {k:13s}{stat(res[k])}')
+        gain = ma / mc
+        verdict = 'a gain beyond the spread' if gain - 1.0 > spread else ('SLOWER beyond the spread' if 1.0 - gain > spread else 'NO difference beyond the spread')
+        L.append(f'    fp16_all / fp16_act_res = {gain:.3f} x  (larger spread of the two columns\' rounds: {100 * spread:.1f} % of the median): {verdict}')
+    assert rc.engine._plan.act16 and not ra.engine._plan.act16
+    L.append('')
+    order = ['conv_in']
+    for l in range(1, 6):
+        order += [f'b{l}_0', f'b{l}_1'] + ([f'pool{l}'] if l < 5 else [])
+    for i in range(6, 10):
+        order += [f'upv{i}', f'b{i}_0', f'sc{i}', f'b{i}_1']
+    order.append('conv10')
+    show = ('conv_in', 'b1_0', 'b1_1', 'pool1', 'b5_0', 'b5_1', 'upv6', 'b6_0', 'sc6', 'b6_1', 'upv9', 'b9_0', 'sc9', 'b9_1', 'conv10')
+    k_all = ('first_fwd', 'conv9_fwd_h1', 'conv9s2_fwd_h1', 'convt_fwd_h1', 'conv1_fwd_h1', 'head_fwd')
+    k_act = ('first_fwd_et', 'conv9_fwd_h1a', 'conv9s2_fwd_h1a', 'convt_fwd_h1a', 'conv1_fwd_h1a', 'head_fwd_et')
+    for label, x in (('16 crops 4x512x512', crops16), ('1 crop 4x512x512', crop1)):
+        ta = per_layer(ra, x, order, kinds=k_all)
+        tc = per_layer(rc, x, order, kinds=k_act)
+        L.append(f'(b) {label}: launches one by one (events around every launch: sums exceed (a))')
+        for n in show:
+            L.append(f'    {n:8s} {rc.engine._plan[n].fwd:6s} fp16_all {ta[n]:8.1f} us   fp16_act_res {tc[n]:8.1f} us   fp16_all / fp16_act_res = {ta[n] / tc[n]:.3f} x')
+        L.append(f'    all {len(order)} launches: fp16_all {sum(ta.values()):.1f} us, fp16_act_res {sum(tc.values()):.1f} us, ratio {sum(ta.values()) / sum(tc.values()):.3f}')
+    L.append('')
+    with torch.no_grad():
+        ya, yc = ra(crop1), rc(crop1)
+    L.append(f'(c) 512 x 512 crop, fp16_act_res against fp16_all: PSNR {psnr(yc, ya):.1f} dB, max |difference| {float((yc - ya).abs().max()):.2e} of outputs up to {float(ya.abs().max()):.2f}')
+    rng = rc.engine.act16_range()
+    L.append(f'    act16_range: {len(rng)} maps, largest amax {max(r["amax"] for r in rng):.3g} ({max(rng, key=lambda r: r["amax"])["name"]}), overflow flags {sum(r["overflow"] for r in rng)}')
+    text = '\n'.join(L) + '\n'
+    print(text)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=None, help='default: profiles/r7/h1_pointwise.txt, or profiles/r7/act16.txt with --act16')
+    ap.add_argument('--out', default=None, help='default: profiles/r7/h1_pointwise.txt, profiles/r7/act16.txt with --act16, profiles/r7/act16_resunet.txt with --act16-res')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--act16', action='store_true', help="the 'fp16_act' column (fp16 storage of the activations, UNet) beside the three others -> profiles/r7/act16.txt")
+    ap.add_argument('--act16-res', action='store_true', help="the 'fp16_act_res' column (fp16 storage of the activations, ResUnet) beside the three others -> profiles/r7/act16_resunet.txt")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('h1_eval_bench needs the GPU: nothing here is measured without one')
-    a.out = a.out or os.path.join(REPO, 'profiles', 'r7', 'act16.txt' if a.act16 else 'h1_pointwise.txt')
+    a.out = a.out or os.path.join(REPO, 'profiles', 'r7', 'act16_resunet.txt' if a.act16_res else 'act16.txt' if a.act16 else 'h1_pointwise.txt')
+    if a.act16_res:
+        return act16_res_main(a)
     if a.act16:
         return act16_main(a)
     g = torch.Generator(device='cuda').manual_seed(1)
