@@ -835,7 +835,7 @@ int pnnp_range_census_f32(const PnnpCensusJob* jobs /*[device]*/, int njobs, uin
  * (p, q are integers there: it counts a window index from which the key with and without the shift follows) + a finishing launch; DN mode a
  * flags pass, a count pass and the finishing launch.  No synchronisation; 32-bit integer atomics and fixed-order float64 sums: bitwise
  * reproducible.  PNNP_E_UNSUPPORTED before anything is launched: n >= 2^32, wp > PNNP_NOISE_SCORE_MAX_WP, nbins > wp_max + 1, and in pair
- * mode a bl that is not an integer in [0, 512] (the window).  The bl=None branch of the reference (data-dependent edges) is not provided. */
+ * mode a bl that is not an integer in [0, 512] (the window).  The bl=None branch of the reference (data-dependent edges) is pnnp_hist_edges_f64's, below. */
 #define PNNP_NOISE_SCORE_MAX_WP 16383
 #define PNNP_NOISE_SCORE_ROW 8
 int64_t pnnp_noise_score_ws_bytes(int ncrops, int64_t n);
@@ -843,6 +843,30 @@ int pnnp_kl_div_norm_f32(const float* p, const float* q, int ncrops, int64_t n, 
                          void* ws, double* hist, double* result, void* stream);
 int pnnp_noise_score_f32(const float* clean, const float* real, const float* sampled_noise, int ncrops, int64_t n, float s, float bl, int wp,
                          const int* lut, int nbins, void* ws, double* hist, double* result, void* stream);
+
+/* ---------------------------------------------------------------- histogram KL over float edges (csrc/hist_kl.hip)
+ * get_histogram / kl_div_3_data (utils/kld_div.py:145-161, :202-210) and the bl=None branch of kl_div_norm (:166-169): np.histogram's rule
+ * for an array of float64 edges e[0..nbins] -- a sample x with e[0] <= x <= e[nbins] is counted in the largest bin i <= nbins - 1 with
+ * e[i] <= x (half-open bins, the last one closed, equal neighbours give an empty bin); a smaller or larger x and a NaN are in no bin and count
+ * in n only.  The comparison is exact: a float32 sample is widened to float64.  y = counts / n, each array by its own n; over the bins where
+ * both are > 0: kl_fwd = sum yp (log yp - log yq), kl_inv = sum yq (log yq - log yp), kl_sym = (kl_fwd + kl_inv) / 2.
+ *   pnnp_hist_edges_f64   p: [ncrops][n_p], q: [ncrops][n_q] or null; float32 (elem_f64 = 0) or float64 (1), aligned to their element, any
+ *                         length.  edges: [nbins + 1] float64 on the device; PRECONDITION: finite and non-decreasing (the caller checks: the
+ *                         values live on the device).  hint_scale = 0: a binary search per sample; > 0: the edges came from arange, the guess
+ *                         int((x - hint_e0) hint_scale) is corrected against the table until the rule holds (a bad hint costs time only).
+ *                         With q: hist [ncrops][2][nbins], kl [ncrops][3].  Without: hist [ncrops][nbins], kl is not written (may be null).
+ *                         ws: 16-byte aligned, pnnp_hist_edges_ws_bytes(ncrops, nbins) bytes, need not be zeroed.
+ *   pnnp_minmax_f         out: 6 doubles -- min p, max p, min q, max q over the FINITE samples (p's twice without a q; -0.0 reads as 0.0), then
+ *                         1.0 if some sample is a NaN or an inf (else 0.0), then 0.  float32 values are exact in the doubles.
+ * One memset, a count pass and a finishing launch (the range pass: three launches); no synchronisation; 32-bit integer atomics, integer min /
+ * max atomics and fixed-order float64 sums: bitwise reproducible.  PNNP_E_UNSUPPORTED before anything is launched: nbins >
+ * PNNP_HIST_EDGES_MAX_BINS, n_p or n_q >= 2^32.  PNNP_E_INVALID: null or misaligned pointers, ncrops outside 1..65535, n < 1, nbins < 1, a
+ * negative or non-finite hint_scale. */
+#define PNNP_HIST_EDGES_MAX_BINS 16384
+int64_t pnnp_hist_edges_ws_bytes(int ncrops, int nbins);
+int pnnp_hist_edges_f64(const void* p, const void* q, int elem_f64, int ncrops, int64_t n_p, int64_t n_q, const double* edges, int nbins,
+                        double hint_e0, double hint_scale, void* ws, double* hist, double* kl, void* stream);
+int pnnp_minmax_f(const void* p, const void* q, int elem_f64, int64_t n_p, int64_t n_q, void* out, void* stream);
 
 /* ---------------------------------------------------------------- differentiable distribution losses (csrc/ddl.hip)
  * The linearly interpolated empirical CDF of a sample set at ascending points and the losses built on it, with the gradient with respect to

@@ -681,6 +681,23 @@ class NoiseFlowFitStep:
         differences (the crops of a batch have different K and ratio, which a pooled quantile mixes); otherwise the batch is pooled."""
         return self._pair_loss(hr, iso, lambda sampled, noise: self._qloss_of(sampled, noise, q, per_crop), fit=False)
 
+    def kl3(self, hr, iso=1600, bin_edges=None, per_crop=False, return_tensors=False):
+        """``metrics.kl_div_3_data`` (utils/kld_div.py:145-161, the marginal KL that papers on noise models report) between the real noise
+        ``real - hr`` and the proxy's samples, drawn exactly as for ``score``: ``make_pair`` at the step's counters, then
+        ``net.sample(clean=hr/ratio, iso=iso) * ratio`` under ``no_grad``.  Returns ``(kl_fwd, kl_inv, kl_sym)`` as float64 device tensors
+        (0-dim, or [B] with ``per_crop``) without synchronising.  ``bin_edges=None`` uses the Noise Flow edges ``metrics.noise_flow_edges()``
+        = ``concatenate(([-1000.], arange(-0.1, 0.1 + 1e-9, 0.2 / 100), [1000.]))``: 100 bins on [-0.1, 0.1] and two catch-all bins.  The
+        module keeps its mode, nothing is optimised and ``step_count`` does not move.  ``return_tensors=True`` also returns
+        ``(real_noise, sampled)``."""
+        from . import metrics
+        edges = metrics.noise_flow_edges() if bin_edges is None else bin_edges
+        kept = []
+        def of(sampled, noise):
+            kept[:] = [noise, sampled]
+            return metrics.kl_div_3_data(noise, sampled, bin_edges=edges, per_crop=per_crop)
+        res = self._pair_loss(hr, iso, of, fit=False)
+        return (res, tuple(kept)) if return_tensors else res
+
     def qloss_step(self, hr, iso=1600, q=None, per_crop=False, lr=None):
         """One fitting step on ``QuantileLoss``: ``ddl_step`` with the loss of ``qloss``.  Returns the detached 0-dim loss."""
         return self._pair_loss(hr, iso, lambda sampled, noise: self._qloss_of(sampled, noise, q, per_crop), fit=True, lr=lr)
