@@ -953,7 +953,41 @@ int pnnp_isp_process_f32(const float* in, int B, int H, int W, const float* rows
 int pnnp_isp_preview_f32(const float* inputs, const float* output, const float* target, const float* mid_offset, int H, int W,
                          const float* wb /*[host, 4]*/, uint8_t* out_u8, void* stream);
 
-/* ---------------------------------------------------------------- sRGB -> packed raw (csrc/unprocess.hip; data_process/unprocess.py:79-167, 199-207)
+/* ---------------------------------------------------------------- full-resolution render (csrc/demosaic.hip; utils/isp_ops.py:134-158, FastISP)
+ * The reference's FastISP with its one outside call, cv2.cvtColor(COLOR_BAYER_BG2RGB_EA), replaced by the demosaic DEFINED here (parity
+ * with an OpenCV build is not a goal).  Pattern RGGB, output order R, G, B, integer arithmetic on the mosaic S [H][W], H and W even, >= 4.
+ *   Interior, 1 <= y <= H-2, 1 <= x <= W-2:
+ *     R or B site (own colour C, other colour O):  C = S[y][x];
+ *         G = (S[y-1][x] + S[y+1][x] + 1) >> 1  if |S[y][x-1] - S[y][x+1]| > |S[y-1][x] - S[y+1][x]|,
+ *             (S[y][x-1] + S[y][x+1] + 1) >> 1  otherwise (a tie takes the horizontal pair);
+ *         O = (S[y-1][x-1] + S[y-1][x+1] + S[y+1][x-1] + S[y+1][x+1] + 2) >> 2
+ *     G site:  G = S[y][x];  the horizontal neighbours' colour = (S[y][x-1] + S[y][x+1] + 1) >> 1, the vertical neighbours' colour =
+ *         (S[y-1][x] + S[y+1][x] + 1) >> 1: on even rows horizontal is R and vertical B, on odd rows the reverse
+ *   Border:  out[y][x] = out[clamp(y, 1, H-2)][clamp(x, 1, W-2)], the interior formula evaluated at the clamped coordinate.
+ *   pnnp_demosaic_ea_u16   the stencil alone: src u16 [B][H][W] -> dst u16 [B][H][W][3], both device; full-range inputs (sums in 32 bits).
+ *   pnnp_fastisp_f32       one launch of front, stencil and tail.  in: f32 [B][4][h][w] packed planes R, G1, B, G2, device; H = 2h, W = 2w.
+ *                          rows: f32 [B][PNNP_ISP_NPARAM] as for pnnp_isp_process_f32: gains 0 and 2 and the nine matrix entries are read.
+ *                          Front, float32, every operation rounded on its own:  S[2i][2j] = R wb0, S[2i][2j+1] = G1, S[2i+1][2j+1] = B wb2,
+ *                            S[2i+1][2j] = G2;  clamp [0,1];  * 16383.0f;  truncate to uint16.  A NaN gives 0 (DEVIATION: the reference's
+ *                            cast of a NaN is undefined).
+ *                          Tail, float64 as numpy does it in the reference:  v = D / 16383;  (v0 m[r][0] + v1 m[r][1]) + v2 m[r][2] per matrix
+ *                            row r, the matrix entries widened to float64;  clamp [0,1];  ^ (1 / 2.2), evaluated to 1e-10 relative (a float32
+ *                            estimate and one float64 Newton step on y^11 = v^5) and, where 255 y lies within 1e-6 of an integer, as
+ *                            exp(log(v) / 2.2) to 1e-14.
+ *                            With PNNP_FASTISP_SONY_CCM the matrix is the reference's default (isp_ops.py:151-153), a float64 constant
+ *                            that the float32 table cannot carry, and the table's matrix entries are not read.
+ *                          Outputs, each optional (NULL skips it, one is required): out_f32 f32 [B][3][H][W] = float32(v64) (DEVIATION: the
+ *                            reference returns float64); out_u8 [B][H][W][3] = floor(255 v64), RGB or, with PNNP_ISP_BGR, BGR.  Both
+ *                            come from the same float64 value: the bytes do not depend on whether the planes are asked for.
+ * Vector stores (16 B per lane and float plane, three dwords of bytes, 24 B of uint16) when W % 4 == 0 and every output starts 16-byte aligned;
+ * otherwise the same arithmetic with element stores.  PNNP_E_INVALID: a null input, rows or (every) output, B < 1, B > 65535, h < 2 or w < 2
+ * (H < 4, W < 4 or an odd side for the stencil alone), 3 H W >= 2^31; a refusal leaves the outputs untouched.
+ * Added under ABI version 9 (entries only): a binding finds an older library by the missing symbol. */
+#define PNNP_FASTISP_SONY_CCM 0x4u /* the tail's matrix is the reference's float64 default */
+int pnnp_demosaic_ea_u16(const uint16_t* src, int B, int H, int W, uint16_t* dst, void* stream);
+int pnnp_fastisp_f32(const float* in, int B, int h, int w, const float* rows, unsigned flags, float* out_f32, uint8_t* out_u8, void* stream);
+
+/* ---------------------------------------------------------------- sRGB -> packed raw(csrc/unprocess.hip; data_process/unprocess.py:79-167, 199-207)
  * The reference's `unprocess()` arithmetic and its `mosaic` / `mosaic_GBRG` gathers, one streaming pass per pixel, one launch per call.
  *   in        device; in_kind says what it holds:  PNNP_UNP_IN_HWC_F32  f32 [B][H][W][3] (the reference's layout: apply_ccm and safe_invert_gains
  *             work on the last axis);  PNNP_UNP_IN_CHW_F32  f32 [B][3][H][W] planes;  PNNP_UNP_IN_HWC_U8  uint8 [B][H][W][3], taken as

@@ -136,6 +136,18 @@ def predict(net, raw, wp, bl, patch_size, base=64, bias=None, tile_batch=None, p
     return forward_tiled(net, packed[None], patch_size, base=base, tile_batch=tile_batch, precision=precision)[0]
 
 
+def predict_rgb(net, raw, wp, bl, patch_size, wb, ccm, base=64, tile_batch=None, precision=None, bgr=False):
+    """Raw file in, full-resolution picture out, without leaving the device: ``predict``, a clamp to [0,1], then the full-resolution
+    render (process.fastisp_render) with the gains ``wb`` [4] and the matrix ``ccm`` [3,3] -> uint8 [H,W,3] device tensor, RGB or
+    (``bgr``) BGR."""
+    from . import process
+    dn = predict(net, raw, wp, bl, patch_size, base=base, tile_batch=tile_batch, precision=precision)
+    if dn.shape[0] != 4:
+        raise PnnpError(f'predict_rgb needs a network that returns packed RGBG frames, got {tuple(dn.shape)}')
+    rows = process.isp_rows(wb, ccm, 1, dn.device)
+    return process.fastisp_render(dn.clamp(0, 1)[None], rows, f32=False, u8=True, bgr=bgr)[1][0]
+
+
 def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None, tiles=None,
              precision=None):
     """-> dict(dn=<clamped (and corrected) prediction>, lr=<clamped input>, metrics=<device tensor [PSNR_dn, SSIM_dn, PSNR_lr, SSIM_lr]>).
@@ -146,7 +158,9 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
     ``render=dict(wb=<4 gains>, ccm=<3x3>, bgr=False)`` (C must be 4) adds ``rgb=dict(lr=, dn=, hr=)``, uint8 [H,W,3] device tensors of
     ``lr``, ``dn`` and ``imgs_hr`` through process.raw2rgb_v2's kernel, and ``metrics_rgb``, a device tensor [PSNR_dn, SSIM_dn, PSNR_lr,
     SSIM_lr] of ``quality_assess`` on the float renders.  ``rows=`` in the dictionary takes a table from process.isp_rows instead of
-    wb / ccm.  Still nothing synchronises; without ``render`` nothing changes.
+    wb / ccm.  Still nothing synchronises; without ``render`` nothing changes.  ``full=True`` in the dictionary renders at full resolution
+    instead (process.fastisp_render, the reference's FastISP): ``rgb`` then holds uint8 [2H,2W,3] and ``metrics_rgb`` scores the
+    full-resolution float renders, the resolution at which the reference's logs report them; without the key nothing changes.
 
     ``tiles=dict(patch_size=, base=64, tile_batch=None)``: the network runs over the frame in overlapping tiles (``forward_tiled``; the
     reference's strategy for frames that do not fit, trainer_SID.py:209-218) instead of in one forward: the reflect-pad-4 branch is not
@@ -226,9 +240,10 @@ def _render(render, lr, dn, hr):
     if rows is None:
         rows = process.isp_rows(render['wb'], render['ccm'], 1, lr.device)
     bgr = bool(render.get('bgr', False))
+    full = bool(render.get('full', False))                     # the full-resolution render (csrc/demosaic.hip) instead of the binned one
     f, b = {}, {}
     for k, t in (('lr', lr), ('dn', dn), ('hr', hr)):
-        f[k], u8 = process.isp_render(t, rows, f32=True, u8=True, bgr=bgr)
+        f[k], u8 = process.fastisp_render(t, rows, f32=True, u8=True, bgr=bgr) if full else process.isp_render(t, rows, f32=True, u8=True, bgr=bgr)
         b[k] = u8[0]
     return dict(rgb=b, metrics_rgb=torch.cat([quality_assess(f['dn'], f['hr']), quality_assess(f['lr'], f['hr'])]))
 

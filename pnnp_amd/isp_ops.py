@@ -5,6 +5,8 @@ Mirrors utils/isp_ops.py:57-112 of the reference.  Inputs may be numpy arrays
 (like the reference's DataLoader workers pass) or CUDA tensors; numpy inputs are
 staged to the GPU, processed there and returned as numpy, CUDA tensors stay on the
 device.  There is no CPU implementation here.
+
+``FastISP`` / ``SimpleISP`` (utils/isp_ops.py:125-158) and ``demosaic_ea`` are the full-resolution render, csrc/demosaic.hip.
 """
 import ctypes as C
 
@@ -108,3 +110,63 @@ def rows2bayer(rows):
     out = torch.empty((2 * h, W), dtype=torch.float64, device=x.device)
     _lib.check(_lib.lib().pnnp_rows_to_bayer(_lib.ptr(x), _lib.ptr(out), h, W, 8, _lib.stream()), 'rows2bayer')
     return _ret(out, host)
+
+
+# ---------------------------------------------------------------------------- full-resolution render (csrc/demosaic.hip)
+def demosaic_ea(mosaic_u16, out=None):
+    """The edge-aware RGGB demosaic that include/pnnp_hip.h defines (the stand-in for cv2.cvtColor(COLOR_BAYER_BG2RGB_EA); parity with an
+    OpenCV build is not a goal): uint16 [H,W] or [B,H,W], H and W even and at least 4, numpy or a tensor -> uint16 [..,H,W,3] in R, G, B
+    order; numpy in -> numpy out.  ``out``: a contiguous uint16 device tensor of the result's shape to write into."""
+    x, host = _to_dev(mosaic_u16)
+    if x.dtype != torch.uint16 or x.dim() not in (2, 3):
+        raise _lib.PnnpError(f'demosaic_ea: expected uint16 [H,W] or [B,H,W], got {x.dtype} {tuple(x.shape)}')
+    batched = x.dim() == 3
+    x3 = x if batched else x[None]
+    B, H, W = x3.shape
+    if H < 4 or W < 4 or H % 2 or W % 2:
+        raise _lib.PnnpError(f'demosaic_ea: a Bayer frame has even sides of at least 4, got {H}x{W}')
+    shape = (B, H, W, 3) if batched else (H, W, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint16, device=x.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise _lib.PnnpError(f'demosaic_ea: out must be a contiguous uint16 device tensor {shape}')
+    try:
+        entry = _lib.lib().pnnp_demosaic_ea_u16
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_demosaic_ea_u16: an older build of the library; rebuild it') from None
+    _lib.check(entry(_lib.ptr(x3), B, H, W, _lib.ptr(out), _lib.stream()), 'demosaic_ea')
+    return _ret(out, host)
+
+
+def FastISP(img4c, wb=None, ccm=None, gamma=2.2, device_out=False, u8=False, bgr=False):
+    """utils/isp_ops.py:134-158 in one kernel: packed [4,h,w] (planes R, G1, B, G2; numpy, staged through the GPU, or a tensor) -> the
+    full-resolution sRGB picture [2h,2w,3], numpy unless ``device_out``.  wb: the gains wb[0] and wb[2] are taken as float32 (None: 2
+    and 2); ccm: [3,3], rounded to float32 and widened (None: the reference's float64 Sony matrix, exactly).  ``u8=True`` returns
+    floor(255 v) as uint8 instead (``bgr=True``: in B, G, R order).
+    Deviations: the result is float32 (float32 of the float64 value; the reference returns float64); a NaN renders as 0; the demosaic is
+    the one include/pnnp_hip.h defines, not OpenCV's; only gamma 2.2 has a kernel, another value raises PnnpError('unsupported ...')."""
+    from . import process
+    process._check_gamma(gamma)
+    x, _ = _to_dev(img4c.detach() if torch.is_tensor(img4c) else img4c)
+    if x.dim() != 3 or x.shape[0] != 4:
+        raise _lib.PnnpError(f'FastISP: expected packed raw [4,h,w], got {tuple(x.shape)}')
+    if wb is None:
+        gains = [2.0, 1.0, 2.0, 1.0]
+    else:
+        g = torch.as_tensor(wb).detach().to(torch.float32).reshape(-1)
+        gains = torch.stack([g[0], torch.ones_like(g[0]), g[2], torch.ones_like(g[0])])
+    rows = process.isp_rows(gains, torch.eye(3) if ccm is None else ccm, 1, x.device)
+    out_f, out_b = process.fastisp_render(x[None], rows, f32=not u8, u8=u8, bgr=bgr, default_ccm=ccm is None)
+    out = out_b[0] if u8 else out_f[0].permute(1, 2, 0)
+    return out if device_out else out.cpu().numpy()
+
+
+def SimpleISP(raw, bl=512, wp=16383, wb=[2, 1, 1, 2], gamma=2.2, device_out=False):
+    """utils/isp_ops.py:125-132 as torch ops on the device (not a kernel, not on the path: here so the module is complete): [h,w,4]
+    RGGB -> float64 [h,w,3] = clip((float32(raw) - bl) / (wp - bl) * wb, 0, 1)[..., (0, 1, 3)] ** (1 / gamma); numpy unless ``device_out``."""
+    x, _ = _to_dev(raw.detach() if torch.is_tensor(raw) else raw)
+    # (a division by a host scalar would run as a multiplication by its reciprocal: divide by a device value, as numpy divides)
+    v = (x.to(torch.float32) - bl) / torch.tensor(float(wp - bl), dtype=torch.float32, device=x.device)
+    g =torch.as_tensor(np.asarray(wb, np.float64), device=x.device)
+    v = (v.to(torch.float64) * g.reshape(1, 1, -1)).clamp(0, 1)[:, :, (0, 1, 3)] ** (1 / gamma)
+    return v if device_out else v.cpu().numpy()

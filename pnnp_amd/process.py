@@ -8,6 +8,7 @@ the fused HIP sampler (csrc/noise.hip); there is no CPU implementation here.
 
 Rendering (data_process/process.py:104-184): ``process``, ``raw2rgb_v2``, ``gamma_compression`` and the trainers' ``preview_strip`` run
 the render kernel (csrc/isp.hip); ``apply_gains``, ``apply_ccms``, ``raw2LRGB`` are torch ops on device tensors, not on the path.
+``fastisp_render`` is the batched full-resolution render (csrc/demosaic.hip; ``isp_ops.FastISP`` has the reference's name).
 """
 import ctypes as C
 
@@ -596,6 +597,37 @@ def isp_render(images, rows=None, f32=True, u8=False, bgr=False, gamma_only=Fals
         raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_isp_process_f32: an older build of the library; rebuild it') from None
     flags = (ISP_F_BGR if bgr else 0) | (ISP_F_GAMMA_ONLY if gamma_only else 0)
     _lib.check(entry(_lib.ptr(x), N, H, W, _lib.ptr(rows), C.c_uint(flags), _lib.ptr(out_f), _lib.ptr(out_b), _lib.stream()), 'isp_process')
+    return out_f, out_b
+
+
+FASTISP_F_SONY_CCM = 0x4                       # PNNP_FASTISP_SONY_CCM
+
+
+def fastisp_render(images, rows, f32=True, u8=False, bgr=False, default_ccm=False):
+    """One launch of csrc/demosaic.hip over a batch, the full-resolution sibling of ``isp_render``: images f32 [N,4,h,w] packed RGBG on the
+    device, rows from ``isp_rows`` (gains 0 and 2 and the matrix are read) -> (float32 [N,3,2h,2w] or None, uint8 [N,2h,2w,3] RGB / BGR or
+    None): the reference's FastISP (utils/isp_ops.py:134-158) with the demosaic that include/pnnp_hip.h defines.  ``default_ccm``: the
+    tail uses the reference's default matrix, a float64 constant that the float32 table cannot carry (the table's matrix is not read).
+    A non-contiguous or non-float32 input is copied to a contiguous float32 tensor first; the input is never written."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 4:
+        raise _lib.PnnpError(f'fastisp render: expected a tensor [N,4,h,w], got {tuple(images.shape) if hasattr(images, "shape") else type(images)}')
+    if not (f32 or u8):
+        raise _lib.PnnpError('fastisp render: no output asked for')
+    _lib.require_cuda(images, rows)
+    N, _, h, w = images.shape
+    if rows is None or rows.dtype != torch.float32 or tuple(rows.shape) != (N, ISP_NPARAM) or not rows.is_contiguous():
+        raise _lib.PnnpError(f'fastisp render: rows must be contiguous float32 [{N},{ISP_NPARAM}] (process.isp_rows)')
+    if h < 2 or w < 2:
+        raise _lib.PnnpError(f'fastisp render: a packed frame of at least 2x2, got {h}x{w}')
+    x = images.detach().contiguous().float()
+    try:
+        entry = _lib.lib().pnnp_fastisp_f32
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_fastisp_f32: an older build of the library; rebuild it') from None
+    out_f = torch.empty((N, 3, 2 * h, 2 * w), dtype=torch.float32, device=x.device) if f32 else None
+    out_b = torch.empty((N, 2 * h, 2 * w, 3), dtype=torch.uint8, device=x.device) if u8 else None
+    flags = (ISP_F_BGR if bgr else 0) | (FASTISP_F_SONY_CCM if default_ccm else 0)
+    _lib.check(entry(_lib.ptr(x), N, h, w, _lib.ptr(rows), C.c_uint(flags), _lib.ptr(out_f), _lib.ptr(out_b), _lib.stream()), 'fastisp')
     return out_f, out_b
 
 
