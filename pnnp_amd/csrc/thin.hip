@@ -192,8 +192,10 @@ struct FirstW {
     int B, H, W, gcs, xcs, tiles_w, ntiles;
 };
 
+// (three waves per SIMD = the three workgroups per CU the 52 KB of LDS admit: without the second bound the column select below is scheduled into 174 VGPRs,
+// two waves per SIMD, and the kernel loses 4 %)
 template <int CO>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 3)
 first_wgrad_kernel(FirstW a) {
     constexpr int NS = 256 / CO, TR = 2 * NS;    // streams; tile rows
     constexpr int NX = (TR + 2) * FW_LW, NLD = (NX + 255) / 256;
@@ -260,14 +262,15 @@ first_wgrad_kernel(FirstW a) {
 #pragma unroll
             for (int u = 0; u < 12; u += 3) {
                 const int wc = c0 + u;           // tile column of the first of three steps; LDS column = tile column + 1
-                const float m0 = wc < nw ? 1.f : 0.f, m1 = wc + 1 < nw ? 1.f : 0.f, m2 = wc + 2 < nw ? 1.f : 0.f;
-                pixels(s2, s0, s1, gr[0][u] * m0, gr[1][u] * m0);
+                // a select, not a multiplication by 0: the value read for a column past nw is column 0's, and inf x 0 would poison dW[co]
+                const bool m0 = wc < nw, m1 = wc + 1 < nw, m2 = wc + 2 < nw;
+                pixels(s2, s0, s1, m0 ? gr[0][u] : 0.f, m0 ? gr[1][u] : 0.f);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s2[r] = xr[r * FW_LW + wc + 3];
-                pixels(s0, s1, s2, gr[0][u + 1] * m1, gr[1][u + 1] * m1);
+                pixels(s0, s1, s2, m1 ? gr[0][u + 1] : 0.f, m1 ? gr[1][u + 1] : 0.f);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s0[r] = xr[r * FW_LW + wc + 4];
-                pixels(s1, s2, s0, gr[0][u + 2] * m2, gr[1][u + 2] * m2);
+                pixels(s1, s2, s0, m2 ? gr[0][u + 2] : 0.f, m2 ? gr[1][u + 2] : 0.f);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s1[r] = xr[r * FW_LW + wc + 5];
             }
