@@ -1019,6 +1019,54 @@ int pnnp_fastisp_f32(const float* in, int B, int h, int w, const float* rows, un
 int pnnp_unprocess_f32(const void* in, int in_kind, int B, int H, int W, const float* rows, unsigned flags, float* out_rgb /*or NULL*/,
                        float* out_packed /*or NULL*/, void* stream);
 
+/* ---------------------------------------------------------------- classical raw filters (csrc/isp_algos.hip; utils/isp_algos.py, isp_ops.py:70-74,115-123)
+ * The reference's VST / inverse_VST, GuidedFilter, FastGuidedFilter, stdfilt, bayer2gray and repair_bad_pixels.  Their OpenCV calls are
+ * replaced by the definitions below (parity with an OpenCV build is not a goal).  Images are N planes of H x W float32 addressed by element
+ * strides {plane, row, pixel} (row and pixel >= 1): contiguous planes are {H W, W, 1}, channel-last data [H][W][C] is {1, W C, C}.
+ *   BOX MEAN  window d x d, d odd, 1 <= d <= 51, anchor at the centre; border REPLICATE (aaa|abc|ccc, the default) or, with
+ *             PNNP_BOX_REFLECT_101, cb|abc|cb, which needs d / 2 < min(H, W).  The d^2 values are summed in float64 (row sums first, each
+ *             sum started at its first term, no running sums), multiplied by the float64 constant 1.0 / (d d) and rounded once to float32.
+ *             Products (I I, I p, x x) are rounded to float32 before they are widened.  Everything after the means is float32, every
+ *             operation rounded on its own, division and square root IEEE.
+ *   pnnp_guided_ab_f32     mu_p, mu_I, II = box(I I), Ip = box(I p);  var = II - mu_I mu_I;  cov = Ip - mu_I mu_p;  a = cov / (var + eps);
+ *                          b = mu_p - a mu_I.  a, b: contiguous planes [N][H][W].  p == I (the same pointer) skips the duplicate means,
+ *                          bitwise the same result.  With PNNP_BOX_HALF (H and W even; the border is REFLECT_101) p and I are read through
+ *                          the 0.5x bilinear resize, the mean f32(f32(x00 + x01) 0.25f + f32(x10 + x11) 0.25f) of each 2 x 2 block, and a, b are [N][H/2][W/2].
+ *   pnnp_guided_apply_f32  out = box(a) I + box(b), out addressed by its own strides.  With PNNP_BOX_HALF a, b are [N][H/2][W/2]; their
+ *                          means (REFLECT_101) go to `workspace` (2 N H/2 W/2 floats, device; NULL otherwise) and are upsampled by 2
+ *                          with INTER_LINEAR's rule: source coordinate (x + 0.5) / 2 - 0.5, weights 0.75 / 0.25, at both ends the weight
+ *                          of the missing neighbour is 0; horizontal pass first; each pass s0 (1 - w) + s1 w in float32.
+ *   pnnp_stdfilt_f32       sqrt(max(box(x x) - box(x)^2, 0)) with REFLECT_101 (a NaN stays a NaN).
+ *   pnnp_vst_f32           n contiguous elements.  inverse = 0 (the generalised Anscombe transform as the reference writes it, `wp` only
+ *                          divides):  t = ((f32(gain) x + f32(gain^2 3 / 8)) + f32(sigma^2)) - f32(gain mu);  y = sqrt(max(t, 0)) / f32(wp);
+ *                          out = f32(2 / gain) y.  inverse = 1:  x = x f32(wp);  y = ((x / 2)^2 - 0.375f) - f32(sigma^2 / gain^2);
+ *                          out = (y f32(gain)) / f32(wp); mu is not added back, as in the reference.  The constants are formed in double.
+ *                          scale (device, NULL: none): one float per `group` consecutive elements; forward transforms f32(x scale),
+ *                          inverse returns f32(out / scale).
+ *   pnnp_bayer2gray_f32    src f32 [B][H][W] -> dst: the 3 x 3 filter [1 2 1; 2 4 2; 1 2 1] / 16 with BORDER_REFLECT (cba|abc|cba): nine exact
+ *                          float64 products summed in row-major order, rounded once.
+ *   pnnp_repair_bad_pixels raw: one mosaic [H][W] (both even) of elem_size 2 (uint16) or 4 (float32), repaired IN PLACE at the n points
+ *                          (row, col), int32 [n][2] on the device: the median of the 3 x 3 neighbourhood in the point's own colour plane
+ *                          (stride 2 in the mosaic, REPLICATE at the plane's border), every median taken from the unmodified frame (two
+ *                          launches through `tmp`, n elements of elem_size, device).  Duplicates allowed; n = 0 launches nothing.  A point
+ *                          outside the frame is the caller's to refuse (the kernels skip it).  A NaN in a float32 neighbourhood is not
+ *                          supported: the compare-exchange network does not put it last as a sort does, and the median is then unspecified.
+ * PNNP_E_INVALID before any launch, outputs untouched: a null or misaligned pointer, N or B outside 1..65535, H or W < 1 or > 2^24, d even or
+ * outside 1..51, REFLECT_101 with d / 2 >= min(H, W), odd H or W with PNNP_BOX_HALF (or for the repair), an unknown flag, a NaN eps, gain or wp 0.
+ * All kernels are scratch-free and use vector accesses only.  Added under ABI version 9 (entries only). */
+#define PNNP_BOX_REFLECT_101 0x1u /* border cb|abc|cb instead of aaa|abc|ccc */
+#define PNNP_BOX_HALF 0x2u        /* FastGuidedFilter: a, b at half resolution */
+int pnnp_guided_ab_f32(const float* p, const float* I, int N, int H, int W, const int64_t* strides /*[host, 3]*/, int d, float eps, unsigned flags,
+                       float* a_out, float* b_out, void* stream);
+int pnnp_guided_apply_f32(const float* a_in, const float* b_in, const float* I, int N, int H, int W, const int64_t* i_strides /*[host, 3]*/, int d,
+                          unsigned flags, float* workspace /*or NULL*/, float* out, const int64_t* out_strides /*[host, 3]*/, void* stream);
+int pnnp_stdfilt_f32(const float* x, int N, int H, int W, const int64_t* strides /*[host, 3]*/, int k, float* out,
+                     const int64_t* out_strides /*[host, 3]*/, void* stream);
+int pnnp_vst_f32(const float* x, int64_t n, int inverse, double sigma, double mu, double gain, double wp, const float* scale /*or NULL*/,
+                 int64_t group, float* out, void* stream);
+int pnnp_bayer2gray_f32(const float* src, int B, int H, int W, float* dst, void* stream);
+int pnnp_repair_bad_pixels(void* raw, int elem_size, int H, int W, const int32_t* points, int n, void* tmp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

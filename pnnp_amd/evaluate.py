@@ -149,7 +149,7 @@ def predict_rgb(net, raw, wp, bl, patch_size, wb, ccm, base=64, tile_batch=None,
 
 
 def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=True, epoch=-1, corrector=None, with_lr=True, render=None, tiles=None,
-             precision=None):
+             precision=None, baseline=None):
     """-> dict(dn=<clamped (and corrected) prediction>, lr=<clamped input>, metrics=<device tensor [PSNR_dn, SSIM_dn, PSNR_lr, SSIM_lr]>).
 
     ``imgs_lr``, ``imgs_hr``: CUDA [1,C,H,W] (the eval loaders use batch_size 1); ``ratio``: scalar / [1] tensor, needed when
@@ -168,9 +168,41 @@ def evaluate(net, imgs_lr, imgs_hr, ratio=None, ori=False, brightness_correct=Tr
     that is the same; without ``tiles`` nothing changes.
 
     ``precision``: None / 'fp32' / 'fp16' / 'fp16_all' for the network forward of this call, as in ``forward_tiled``; the engine's previous setting is restored
-    afterwards, also when the call raises."""
+    afterwards, also when the call raises.
+
+    ``baseline=dict(gain=, sigma=, wp_bl=, d=7, eps=1.0)``: the input frame is also denoised by the non-learned baseline
+    (isp_algos.vst_denoise: VST -> guided filter -> inverse VST; ``gain`` and ``sigma`` in DN, ``wp_bl`` = white point minus black level)
+    at ``scale = float32(wp_bl) / float32(ratio)`` (one float32 division, however ``ratio`` is passed: a float, a host or a device tensor), or ``wp_bl`` with ``ori`` (the frame is then multiplied by ``ratio`` as the prediction is), clamped to
+    [0, 1] like the prediction, and scored: the result gains ``base`` (the frame) and ``psnr_base`` / ``ssim_base`` (device scalars, its
+    ``quality_assess`` against ``imgs_hr``).  None (the default): nothing changes."""
     with _precision(net, precision):
-        return _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles)
+        res = _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles)
+    if baseline is not None:
+        res.update(_baseline(baseline, imgs_lr, imgs_hr, ratio, ori))
+    return res
+
+
+def _baseline(baseline, imgs_lr, imgs_hr, ratio, ori):
+    """the ``baseline=`` part of ``evaluate``: four launches of csrc/isp_algos.hip, one of the PSNR / SSIM kernel"""
+    from . import isp_algos
+    unknown = set(baseline) - {'gain', 'sigma', 'wp_bl', 'd', 'eps'}
+    if unknown or not {'gain', 'sigma', 'wp_bl'} <= set(baseline):
+        raise PnnpError(f'evaluate(baseline=...) takes gain, sigma, wp_bl and optionally d, eps; got {sorted(baseline)}')
+    if ratio is None:
+        raise PnnpError('evaluate(baseline=...) needs the ratio: the frame is brought back to DN with wp_bl / ratio')
+    wp_bl = float(baseline['wp_bl'])
+    with torch.no_grad():
+        x = imgs_lr.contiguous().float()
+        # one rule however the ratio arrives: a float32 value on the device, scale = float32(wp_bl) / float32(ratio) as a float32 division
+        # (a device ratio stays on the device: nothing here synchronises)
+        r = torch.as_tensor(ratio).detach().reshape(-1)[:1].to(device=x.device, dtype=torch.float32)
+        scale = torch.full_like(r, wp_bl) if ori else torch.full_like(r, wp_bl) / r
+        base = isp_algos.vst_denoise(x, baseline['gain'], baseline['sigma'], d=baseline.get('d', 7), eps=baseline.get('eps', 1.0), scale=scale, layout='chw')
+        if ori:
+            base = base * r
+        base = base.clamp(0, 1)
+        m = quality_assess(base, imgs_hr)
+    return dict(base=base, psnr_base=m[0], ssim_base=m[1])
 
 
 def _evaluate(net, imgs_lr, imgs_hr, ratio, ori, brightness_correct, epoch, corrector, with_lr, render, tiles):
@@ -266,10 +298,12 @@ class EvalLoop:
     """Accumulates what `SID_Trainer.eval` reports over a dataset: `metrics` (name -> [PSNR, SSIM], the content of
     metrics.pkl) and the log line of trainer_SID.py:309-312."""
 
-    def __init__(self, net, ori=False, brightness_correct=True, tiles=None, precision=None):
+    def __init__(self, net, ori=False, brightness_correct=True, tiles=None, precision=None, baseline=None):
         """``tiles``: as in ``evaluate`` (every frame of the dataset runs in overlapping tiles); None: whole frames.  ``precision``: as in ``evaluate``,
-        for every step (the switch is set and restored per step: with another precision than the engine's own, set it on the engine once instead)"""
+        for every step (the switch is set and restored per step: with another precision than the engine's own, set it on the engine once instead).
+        ``baseline``: as in ``evaluate``, for every step; the log then gains a line with the baseline's averages (None: the log is unchanged)"""
         self.net, self.ori, self.brightness_correct, self.tiles, self.precision = net, ori, brightness_correct, tiles, precision
+        self.baseline = baseline
         self.corrector = IlluminanceCorrect()
         self.reset()
 
@@ -279,13 +313,18 @@ class EvalLoop:
         self.psnr_lr, self.ssim_lr = AverageMeter(), AverageMeter()
         self.rgb_psnr, self.rgb_ssim = AverageMeter(), AverageMeter()                # RGB-domain meters: only steps that rendered count
         self.rgb_psnr_lr, self.rgb_ssim_lr = AverageMeter(), AverageMeter()
+        self.psnr_base, self.ssim_base = AverageMeter(), AverageMeter()              # the non-learned baseline: only with ``baseline``
         self._pending = []
         self._pending_rgb = []
+        self._pending_base = []
 
     def step(self, name, imgs_lr, imgs_hr, ratio=None, epoch=-1, render=None):
         out = evaluate(self.net, imgs_lr, imgs_hr, ratio=ratio, ori=self.ori, brightness_correct=self.brightness_correct,
-                       epoch=epoch, corrector=self.corrector, render=render, tiles=self.tiles, precision=self.precision)
+                       epoch=epoch, corrector=self.corrector, render=render, tiles=self.tiles, precision=self.precision,
+                       **({} if self.baseline is None else dict(baseline=self.baseline)))
         self._pending.append((name, out['metrics']))          # device tensors: one host sync per dataset, in finish()
+        if self.baseline is not None:
+            self._pending_base.append(torch.stack([out['psnr_base'], out['ssim_base']]))
         if render is not None:
             self._pending_rgb.append(out['metrics_rgb'])
         return out
@@ -304,10 +343,16 @@ class EvalLoop:
                 self.rgb_psnr.update(p_dn); self.rgb_ssim.update(s_dn)
                 self.rgb_psnr_lr.update(p_lr); self.rgb_ssim_lr.update(s_lr)
             self._pending_rgb = []
+        if self._pending_base:
+            for p_b, s_b in torch.stack(self._pending_base).cpu().tolist():
+                self.psnr_base.update(p_b); self.ssim_base.update(s_b)
+            self._pending_base = []
         text = (f"Epoch {epoch}: PSNR={self.psnr.avg:.2f}\n"
                 f"psnrs_lr={self.psnr_lr.avg:.2f}, psnrs_dn={self.psnr.avg:.2f}"
                 f"\nssims_lr={self.ssim_lr.avg:.4f}, ssims_dn={self.ssim.avg:.4f}")
         if self.rgb_psnr.count:
             text += (f"\nrgb: psnrs_lr={self.rgb_psnr_lr.avg:.2f}, psnrs_dn={self.rgb_psnr.avg:.2f}, "
                      f"ssims_lr={self.rgb_ssim_lr.avg:.4f}, ssims_dn={self.rgb_ssim.avg:.4f}")
+        if self.psnr_base.count:
+            text += f"\nbaseline (VST + guided filter): psnrs_base={self.psnr_base.avg:.2f}, ssims_base={self.ssim_base.avg:.4f}"
         return self.metrics, text

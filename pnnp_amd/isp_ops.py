@@ -7,6 +7,7 @@ staged to the GPU, processed there and returned as numpy, CUDA tensors stay on t
 device.  There is no CPU implementation here.
 
 ``FastISP`` / ``SimpleISP`` (utils/isp_ops.py:125-158) and ``demosaic_ea`` are the full-resolution render, csrc/demosaic.hip.
+``bayer2gray`` and ``repair_bad_pixels`` (utils/isp_ops.py:70-74, 115-123) run on csrc/isp_algos.hip.
 """
 import ctypes as C
 
@@ -170,3 +171,58 @@ def SimpleISP(raw, bl=512, wp=16383, wb=[2, 1, 1, 2], gamma=2.2, device_out=Fals
     g =torch.as_tensor(np.asarray(wb, np.float64), device=x.device)
     v = (v.to(torch.float64) * g.reshape(1, 1, -1)).clamp(0, 1)[:, :, (0, 1, 3)] ** (1 / gamma)
     return v if device_out else v.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------- the OpenCV-backed helpers (csrc/isp_algos.hip)
+def bayer2gray(raw):
+    """utils/isp_ops.py:70-74: the bilinear Bayer-to-gray filter, [1 2 1; 2 4 2; 1 2 1] / 16 with BORDER_REFLECT, on a float32 mosaic [H,W]
+    (or a batch [B,H,W]): nine exact float64 products, their sum rounded once (include/pnnp_hip.h defines it; parity with an OpenCV build
+    is not a goal).  A uint16 mosaic is refused (OpenCV would return a saturated uint16 image: convert first).  numpy in -> numpy out."""
+    if getattr(raw, 'dtype', None) not in (torch.float32, np.dtype('float32')):
+        raise _lib.PnnpError(f'bayer2gray: expected a float32 mosaic, got {getattr(raw, "dtype", type(raw))}')
+    if raw.ndim not in (2, 3) or 0 in tuple(raw.shape):
+        raise _lib.PnnpError(f'bayer2gray: expected [H,W] or [B,H,W], got {tuple(raw.shape)}')
+    x, host = _to_dev(raw)
+    B = x.shape[0] if x.dim() == 3 else 1
+    out = torch.empty_like(x)
+    try:
+        entry = _lib.lib().pnnp_bayer2gray_f32
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_bayer2gray_f32: an older build of the library; rebuild it') from None
+    _lib.check(entry(_lib.ptr(x), B, x.shape[-2], x.shape[-1], _lib.ptr(out), _lib.stream()), 'bayer2gray')
+    return _ret(out, host)
+
+
+def repair_bad_pixels(raw, bad_points, method='median'):
+    """utils/isp_ops.py:115-123: every listed pixel of the mosaic ``raw`` [H,W] (uint16 or float32, H and W even; a CONTIGUOUS device
+    tensor) takes the 3 x 3 median of its own colour plane (REPLICATE at the plane's border), every median from the unmodified frame.
+    In place, and returns ``raw``, as the reference does.  ``bad_points``: a sequence of (row, col), or an int tensor [n,2]; duplicates
+    are allowed, an empty list is a no-op, a point outside the frame raises before anything is launched (a device tensor of points is
+    read back for that check: the one synchronisation here; a host list costs none).  ``method`` is ignored, as in the reference.  A NaN in a float32 neighbourhood is not supported (the median
+    is then unspecified)."""
+    if not torch.is_tensor(raw) or raw.dtype not in (torch.uint16, torch.float32) or raw.dim() != 2:
+        raise _lib.PnnpError(f'repair_bad_pixels: expected a uint16 or float32 tensor [H,W], got {getattr(raw, "dtype", type(raw))} '
+                             f'{tuple(getattr(raw, "shape", ()))}')
+    H, W = raw.shape
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise _lib.PnnpError(f'repair_bad_pixels: a Bayer frame has even sides, got {H}x{W}')
+    if not raw.is_contiguous():
+        raise _lib.PnnpError('repair_bad_pixels works in place: the frame must be contiguous')
+    pts = bad_points.detach() if torch.is_tensor(bad_points) else torch.as_tensor(np.asarray(bad_points, np.int64).reshape(-1, 2))
+    if pts.dim() != 2 or pts.shape[1] != 2 or pts.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+        raise _lib.PnnpError(f'repair_bad_pixels: bad_points must be integer points [n,2], got {pts.dtype} {tuple(pts.shape)}')
+    n = pts.shape[0]
+    if n == 0:
+        return raw
+    host = pts.cpu()
+    if int(host[:, 0].min()) < 0 or int(host[:, 0].max()) >= H or int(host[:, 1].min()) < 0 or int(host[:, 1].max()) >= W:
+        raise _lib.PnnpError(f'repair_bad_pixels: a point lies outside the {H}x{W} frame')
+    _lib.require_cuda(raw)
+    pd = pts.to(device=raw.device, dtype=torch.int32).contiguous()
+    tmp = torch.empty((n,), dtype=raw.dtype, device=raw.device)
+    try:
+        entry = _lib.lib().pnnp_repair_bad_pixels
+    except AttributeError:
+        raise _lib.PnnpError(f'{_lib.LIB_PATH} has no pnnp_repair_bad_pixels: an older build of the library; rebuild it') from None
+    _lib.check(entry(_lib.ptr(raw), raw.element_size(), H, W, _lib.ptr(pd), n, _lib.ptr(tmp), _lib.stream()), 'repair_bad_pixels')
+    return raw
