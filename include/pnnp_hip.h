@@ -1067,6 +1067,33 @@ int pnnp_vst_f32(const float* x, int64_t n, int inverse, double sigma, double mu
 int pnnp_bayer2gray_f32(const float* src, int B, int H, int W, float* dst, void* stream);
 int pnnp_repair_bad_pixels(void* raw, int elem_size, int H, int W, const int32_t* points, int n, void* tmp, void* stream);
 
+/* ---------------------------------------------------------------- dark-frame calibration (csrc/calib.hip; pnnp_amd/calibrate.py)
+ * The two streaming passes over a stack of dark (bias) frames from which pnnp_amd/calibrate.py estimates a camera's noise table, and the
+ * row means that row_denoise needs.  frames: uint16 [n][H][W], a contiguous Bayer mosaic on the device: one chunk of the stack.
+ *   pnnp_calib_accum_u16     one read of the chunk, three exact integer results:
+ *                              sum[y][x]   += sum_f v            int32 [H][W], read and written: the caller zeroes it before the first chunk
+ *                              sumsq[y][x] += sum_f v v          int64 [H][W], likewise
+ *                              rowsum[f][y][c] = sum over x with (x & 1) == c of v     int32 [n][H][2], this chunk's slice, written (never read)
+ *                            A chunk of more than 1024 frames runs as several launches.  The caller keeps the stack's total at or below
+ *                            32768 frames (32768 * 65535 < 2^31, the int32 sum); the entry refuses n > 32768.
+ *   pnnp_calib_residual_u16  out[f][y][x] = (float(v) - ds[y][x]) - rowoff[f][y][x & 1]: two float32 subtractions in that order, each
+ *                            rounded on its own.  ds f32 [H][W], rowoff f32 [n][H][2], out f32 [n][H][W].
+ *   pnnp_calib_rowmean_f32   out[y] = (sum_x map[y][x]) / W in float64, map f32 [H][W], out f64 [H]; one workgroup per row, a fixed order
+ *                            (thread t adds x = t, t + 256, ... in order; the 256 partial sums fold in halves).
+ * 16-byte accesses when W % 8 == 0 and frames, sum, sumsq (ds, out) start 16-byte aligned; otherwise the same arithmetic with element
+ * accesses.  PNNP_E_INVALID before any launch, outputs untouched: a null or misaligned pointer, n outside 1..32768, H or W odd or below 2
+ * (rowmean: below 1), W > 65536 (the int32 row sum), H > 2^24.  All kernels are scratch-free and use vector accesses only.
+ *
+ * THE 1-D BILATERAL FILTER of row_denoise (the stand-in for cv2.bilateralFilter on a 1 x n row; parity with an OpenCV build is not a
+ * goal), float64 on the host over the n row means m:
+ *     out[i] = sum_k w_k m[clamp(i + k, 0, n - 1)] / sum_k w_k,   k = -12 .. 12 (window 25, border REPLICATE),
+ *     w_k = exp(-k^2 / (2 ss^2)) exp(-(m[clamp(i + k)] - m[i])^2 / (2 sc^2)),   sc = 10,  ss = 1 + iso / 200,
+ * the terms added in the order k = -12 .. 12.
+ * Added under ABI version 9 (entries only): a binding finds an older library by the missing symbol. */
+int pnnp_calib_accum_u16(const uint16_t* frames, int n, int H, int W, int32_t* sum_i32, int64_t* sumsq_i64, int32_t* rowsum_i32, void* stream);
+int pnnp_calib_residual_u16(const uint16_t* frames, int n, int H, int W, const float* ds_f32, const float* rowoff_f32, float* out_f32, void* stream);
+int pnnp_calib_rowmean_f32(const float* map, int H, int W, double* out_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

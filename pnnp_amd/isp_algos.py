@@ -5,6 +5,7 @@
     GuidedFilter, FastGuidedFilter
     Blur1D                        torch ops, not on the path
     vst_denoise                   an extension: VST -> GuidedFilter -> inverse_VST, the non-learned baseline denoiser
+    row_denoise                   the row-banding clean-up of a dark-shading map (pnnp_amd/calibrate.py, csrc/calib.hip)
 
 Device tensors in, device tensors out, nothing synchronises.  The image functions take ``[H,W]`` or ``[H,W,C]`` (the reference's layout,
 the default) or, with ``layout='chw'``, ``[..., H, W]``: every plane is filtered on its own.  float32 runs on the kernels; a float64
@@ -12,7 +13,9 @@ input runs as float64 torch ops (not on the path: there so that a float64 caller
 
 The OpenCV calls of the reference are replaced by the definitions in include/pnnp_hip.h (box sums in float64, rounded once): parity with
 an OpenCV build is not a goal.  Deviations: the window ``d`` is odd and at most 51; ``VST`` keeps the reference's quirks (``wp`` only
-divides, ``inverse_VST`` does not add ``mu`` back); ``row_denoise`` (cv2.bilateralFilter) and ``AlgoDebugger`` (a GUI) have no counterpart.
+divides, ``inverse_VST`` does not add ``mu`` back); ``row_denoise`` takes a loaded map only (its ``path`` is not read) and filters the row
+means with the 1-D bilateral filter that include/pnnp_hip.h defines, the stand-in for cv2.bilateralFilter; ``AlgoDebugger`` (a GUI) has
+no counterpart.
 """
 import ctypes as C
 
@@ -239,3 +242,12 @@ def vst_denoise(x, gain, sigma, d=7, eps=1.0, scale=1.0, layout='chw'):
     v = _vst_launch(xc, 0, sigma, 0.0, gain, 1, st, group)
     g = GuidedFilter(v, v, d, eps, layout=layout)
     return _vst_launch(g, 1, sigma, 0.0, gain, 1, st, group)
+
+
+def row_denoise(path, iso, data=None):
+    """utils/isp_algos.py:84-99 with the reference's signature: ``calibrate.row_denoise(data, iso)``.  ``data`` is required: the
+    reference's ``dataload(path)`` is not mirrored, so ``path`` is never read."""
+    if data is None:
+        raise PnnpError('row_denoise: pass the map as data= (a float32 [H,W] tensor or array); files are not read here')
+    from . import calibrate
+    return calibrate.row_denoise(data, iso)

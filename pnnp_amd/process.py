@@ -101,6 +101,45 @@ def _build_specific():
 
 _REG = _build_regression()
 _SPEC = _build_specific()
+_BUILTIN = frozenset(_REG) | frozenset(_SPEC) | frozenset(Dual_ISO_Cameras)
+
+_SPEC_KEYS = ('Kmax', 'lam', 'sigGs', 'sigGssig', 'sigTL', 'sigTLsig', 'sigR', 'sigRsig', 'bias', 'biassig', 'q', 'wp', 'bl')
+_REG_KEYS = ('Kmin', 'Kmax', 'lam', 'q', 'wp', 'bl', 'sigTLk', 'sigTLb', 'sigTLsig', 'sigRk', 'sigRb', 'sigRsig', 'sigGsk', 'sigGsb', 'sigGssig')
+
+
+def register_camera(name, per_iso=None, regression=None):
+    """An extension: add a calibrated camera to the tables the samplers draw from.  ``per_iso``: {iso: row}, rows with the keys of a
+    per-ISO table row (what ``calibrate.fit_dark`` returns; further keys are dropped); ``regression``: a dict with the keys of a
+    regression row (what ``calibrate.fit_regression`` returns).  Afterwards ``get_specific_noise_params(name, iso)``,
+    ``sample_params_max(camera_type=name, iso=)`` and everything that takes a ``camera_type`` work with ``name``.  A built-in name is
+    refused; a name registered before is replaced.  Without ``regression`` a call with ``iso=None`` falls back to NikonD850, as for any
+    unknown camera."""
+    if not isinstance(name, str) or not name:
+        raise ValueError(f'register_camera: the name must be a non-empty string, got {name!r}')
+    if name in _BUILTIN:
+        raise ValueError(f'register_camera: {name!r} is a built-in camera and is not replaced')
+    if per_iso is None and regression is None:
+        raise ValueError('register_camera: give per_iso, regression or both')
+    spec, reg = None, None
+    if per_iso is not None:
+        if not per_iso:
+            raise ValueError('register_camera: per_iso is empty')
+        spec = {}
+        for iso, row in per_iso.items():
+            missing = [k for k in _SPEC_KEYS if k not in row]
+            if missing:
+                raise ValueError(f'register_camera: the row of ISO {iso} lacks {missing}')
+            spec[str(iso)] = {k: (row[k] if k == 'bias' else (int(row[k]) if k in ('wp', 'bl') and float(row[k]).is_integer() else float(row[k])))
+                              for k in _SPEC_KEYS}
+    if regression is not None:
+        missing = [k for k in _REG_KEYS if k not in regression]
+        if missing:
+            raise ValueError(f'register_camera: the regression lacks {missing}')
+        reg = {k: float(regression[k]) for k in _REG_KEYS}
+    if spec is not None:
+        _SPEC[name] = spec
+    if reg is not None:
+        _REG[name] = reg
 
 
 def get_camera_noisy_params(camera_type=None):

@@ -20,6 +20,7 @@ EXTRA = {'wino.hip': ['-fno-slp-vectorize'], 'conv_igemm.hip': ['-fno-slp-vector
          'noise.hip': ['-ffp-contract=off'], 'pack.hip': ['-ffp-contract=off'], 'isp.hip': ['-ffp-contract=off'], 'unprocess.hip': ['-ffp-contract=off'], 'cropaug.hip': ['-ffp-contract=off'], 'noise_score.hip': ['-ffp-contract=off'], 'ddl.hip': ['-ffp-contract=off'], 'quantile.hip': ['-ffp-contract=off'], 'hist_kl.hip': ['-ffp-contract=off'],
          'demosaic.hip': ['-ffp-contract=off'],       # FastISP's float32 front and float64 tail, every operation rounded on its own
          'isp_algos.hip': ['-ffp-contract=off'],      # the classical raw filters: float64 sums, float32 products, means and tails, each rounded as written
+         'calib.hip': ['-ffp-contract=off'],          # the residual's two float32 subtractions, each rounded on its own
          'tiles.hip': ['-ffp-contract=off'],          # the merge's fused tail: (tile * ratio).clamp(0, 1) bit-equal to the tensor ops
          'unet_loss.hip': ['-ffp-contract=off'],      # every rounding of the pooled levels and of the Charbonnier term is the one written
          # the Winograd backward-weight kernel's source order is its schedule (slots fenced with sched_barrier)
