@@ -147,7 +147,16 @@ int pnnp_conv_bwd_data_f32(const float* g, int Cout, const float* w_dgrad,
 /* The same two operators for 3x3 / stride 1 / pad 1 layers through Winograd F(2x2,3x3) (2.25x fewer MFMA passes;
  * results differ from the direct form by fp32 rounding of the transforms, ~1e-6 relative).  Weights are packed by
  * pnnp_pack_conv_weight_wino_f32 into U = G g G^T, 16*Cout*Cin floats each; supported when the channels read are a
- * multiple of 8 and the channels written a multiple of 64 (pnnp_wino_supported). */
+ * multiple of 8 and the channels written a multiple of 64 (pnnp_wino_supported).
+ * Limits (PNNP_E_UNSUPPORTED, nothing is launched): byte offsets inside one image are 32-bit, so H * W * cs * 4 < 2^31 for the widest
+ * of the tensors read AND written (cs = channels per pixel of x1, x2 / g and of y / dx1, dx2; mask and addsrc share the destination's
+ * geometry), and B * H * W * cs < 2^31 for the tensors read.  Destinations, bias, masks and addsrc are 16-byte aligned and the
+ * destinations' channel counts multiples of 4 (PNNP_E_INVALID); dx1 is a multiple of 32 channels when dx2 follows it.
+ * Non-finite values: a tile's 4x4 input patch is mixed by the transforms, so one NaN or inf in x (forward) or g (backward-data)
+ * makes non-finite every output that the direct form makes non-finite, and at most the outputs -- in every channel -- of the 2x2
+ * output tiles (tiles start at even rows and columns) whose 4x4 patch (one pixel of border around the tile) holds that pixel; every
+ * other output is unaffected.  Backward-weight: an inf of g gives a bias gradient of inf in its channel as the plain sum does, leaves
+ * the other channels' dbias and dW rows finite, and makes that channel's dW row non-finite wherever the direct form is. */
 int64_t pnnp_wino_weight_floats(int Cout, int Cin);
 int pnnp_wino_supported(int K_read, int N_written);
 int pnnp_pack_conv_weight_wino_f32(const float* w, float* fwd /*or null*/, float* dgrad /*or null*/, int Cout, int Cin, void* stream);
@@ -159,8 +168,6 @@ int pnnp_conv3x3_wino_bwd_data_f32(const float* g, int Cout, const float* u_dgra
                                    float* dx1, int C1, const float* mask1, int mode1, int accum1,
                                    float* dx2, int C2, const float* mask2, int mode2, int accum2,
                                    int B, int H, int W, void* stream);
-/* Winograd backward-weight (dg = G^T [sum_tiles (A dY A^T) (.) (B^T d B)] G): same contract as
- * pnnp_conv_bwd_weight_f32 with taps = 9; needs H % 4 == 0, W % 8 == 0 and Cout, C1, C2 multiples of 64. */
 /* ---------------------------------------------------------------- weight re-packing, batched (csrc/pack_jobs.hip)
  * The optimiser moves every weight every step (trainer_SID.py:101), so every layer's packed images are rebuilt every step.  A job
  * is one such rebuild; pnnp_pack_jobs_f32 runs a HOST array of jobs in ceil(n / 32) launches.  The builders append the jobs of one
@@ -470,6 +477,10 @@ int pnnp_conv1x1_x3_bwd_weight_f32(const float* g, int g_cs, int Cout, const flo
 /* (The Winograd kernel's cycle-stamp hook `pnnp_wino_set_debug` exists only in profiling builds, -DPNNP_WINO_DEBUG=1: the shipped
  * library exports no debug hook, reads no environment variable and keeps no state between calls besides idempotent per-device
  * caches of device facts and the persistent-split setting above.) */
+/* Winograd backward-weight (dg = G^T [sum_tiles (A dY A^T) (.) (B^T d B)] G): same contract as
+ * pnnp_conv_bwd_weight_f32 with taps = 9; needs H % 4 == 0, W % 8 == 0 and Cout, C1, C2 multiples of 64.
+ * Limits (PNNP_E_UNSUPPORTED, nothing is launched): B * H * W * cs < 2^31 elements and, byte offsets inside one image being 32-bit,
+ * (H * W + W + 1) * cs * 4 < 2^31 for the widest pixel stride cs of g_cs, x1_cs, x2_cs. */
 int pnnp_wino_wgrad_supported(int H, int W, int Cout, int C1, int C2);
 int64_t pnnp_wino_wgrad_workspace_floats(int B, int H, int W, int Cout, int Cin);
 int pnnp_conv3x3_wino_bwd_weight_f32(const float* g, int g_cs, int Cout, const float* x1, int x1_cs, int C1,

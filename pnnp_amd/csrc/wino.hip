@@ -396,10 +396,14 @@ int wino_launch(WinoArgs& a, hipStream_t st) {
     if (a.K % KC || a.N % BN || a.C1 % KC || (a.n_split % 32)) return PNNP_E_UNSUPPORTED;
     if ((int64_t)a.B * a.H * a.W * (a.src_cs[0] > a.src_cs[1] ? a.src_cs[0] : a.src_cs[1]) >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     // buffer-resource addressing: byte offsets inside one image (and inside one channel block of U) are 32-bit, 2^31 marks out-of-range
-    if ((int64_t)a.H * a.W * (a.src_cs[0] > a.src_cs[1] ? a.src_cs[0] : a.src_cs[1]) * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
+    // (the epilogue's ibytes and off[k] are built from dst_cs, which can be 64 times src_cs; the mask and addsrc share the destination's geometry)
+    int max_cs = a.src_cs[0] > a.src_cs[1] ? a.src_cs[0] : a.src_cs[1];
+    if (a.dst_cs[0] > max_cs) max_cs = a.dst_cs[0];
+    if (a.dst_cs[1] > max_cs) max_cs = a.dst_cs[1];
+    if ((int64_t)a.H * a.W * max_cs * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     if ((int64_t)a.K * 16 * BN * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     a.tiles_x = (a.W + 15) / 16; a.tiles_y = (a.H + 15) / 16;
-    // 16-byte epilogue accesses
+    // 16-byte epilogue accesses (the stride half cannot trip through the exported entries: N % 64 and n_split % 32 above make both strides multiples of 32)
     if ((a.dst_cs[0] & 3) || (a.dst_cs[1] & 3) ||
         ((((uintptr_t)a.dst[0]) | ((uintptr_t)a.dst[1]) | ((uintptr_t)a.bias) | ((uintptr_t)a.mask[0]) | ((uintptr_t)a.mask[1]) | ((uintptr_t)a.addsrc)) & 15))
         return PNNP_E_INVALID;

@@ -153,7 +153,10 @@ __global__ void __launch_bounds__(256, 1) wino_wgrad_kernel(WwArgs a) {
         float r[8];
 #pragma unroll
         for (int cc = 0; cc < 8; ++cc) r[cc] = za * y0r[cc] + zb * y1r[cc];
-        bsum = fmaf(wsum, ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])), bsum);   // wave 1: sum of g
+        // wave 1: sum of g.  A select, not wsum * sum: the parked copy of the last chunk (wsum = 0) must not turn an inf of g into 0 x inf = NaN
+        // (wsum is 1.f or 0.f, so finite g gives the fma's bits -- but for the sign of a zero: a bsum of -0 comes out of the parked step as +0)
+        const float rsum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        bsum += wsum != 0.f ? rsum : 0.f;
         float* o = zt + ((i * 4) * 2 + tq) * PLANE + lane * 4;
         *reinterpret_cast<float4*>(o) = make_float4(r[0], r[2], r[4], r[6]);
         *reinterpret_cast<float4*>(o + 2 * PLANE) = make_float4(r[0] + r[1], r[2] + r[3], r[4] + r[5], r[6] + r[7]);
@@ -344,6 +347,9 @@ int pnnp_conv3x3_wino_bwd_weight_f32(const float* g, int g_cs, int Cout, const f
     if (!pnnp_wino_wgrad_supported(H, W, Cout, C1, x2 ? C2 : 0)) return PNNP_E_UNSUPPORTED;
     if (g_cs < Cout || x1_cs < C1 || (x2 && x2_cs < C2) || (g_cs & 3) || (x1_cs & 3) || (x2 && (x2_cs & 3))) return PNNP_E_INVALID;
     if ((int64_t)B * H * W * (g_cs > x1_cs ? g_cs : x1_cs) >= (1ll << 31) || (x2 && (int64_t)B * H * W * x2_cs >= (1ll << 31))) return PNNP_E_UNSUPPORTED;
+    // buffer-resource addressing: sx, sgo, xvoff, gvoff and both num_records are 32-bit BYTE counts inside one image (x: one row + one pixel more), 2^31 marks out-of-range
+    const int max_cs = g_cs > x1_cs ? (x2 && x2_cs > g_cs ? x2_cs : g_cs) : (x2 && x2_cs > x1_cs ? x2_cs : x1_cs);
+    if (((int64_t)H * W + W + 1) * max_cs * 4 >= (1ll << 31)) return PNNP_E_UNSUPPORTED;
     if (workspace_floats < pnnp_wino_wgrad_workspace_floats(B, H, W, Cout, N)) return PNNP_E_WORKSPACE;
     static PnnpPerDevice lds_once;
     if (pnnp_allow_lds(lds_once, wino_wgrad_kernel, SMEM_FLOATS * 4) != PNNP_OK) return PNNP_E_LAUNCH;
